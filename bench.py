@@ -9,8 +9,16 @@ batch: upsample+proj, RoIAlign, xcorr, fused decoders+heads, peaks+decode,
 NMS over each image's exemplar union (+ for N>1 the RCCL all-gather of
 per-image counts and kept boxes that replaces the Hadoop reducer).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(images/s, ms_per_step, the workload).  `--dump-outputs DIR` also writes what
+the last timed step returned (rank 0: DIR/logits.npy, boxes.npy, refs.npy,
+counts.npy); the inputs are seeded, so two builds can be compared output for
+output.  Everything else the benchmark measures -- the kernels' HIP-event
+times and roofline fractions, the per-template-class correlation launches,
+the PMC and bare-loop records, the CPU baseline -- runs only with `--full`.
 
 `python bench.py --gpus N` (N > 1) outside a torch.distributed launch starts
 the N rank processes itself (torch.distributed.run, 127.0.0.1, one per GPU)
@@ -19,7 +27,7 @@ torchrun, WORLD_SIZE must equal --gpus.  The reference's counterparts are
 Lightning DDP over all devices (main.py:108-119) and Hadoop's map-side
 parallelism (mapper.py:51).
 
-Prints one JSON line (rank 0).  `roofline` is the fused decoder kernel
+Prints one JSON line (rank 0).  With `--full`: `roofline` is the fused decoder kernel
 (tmr_conv_heads, >98% of the path's FLOPs) timed with HIP events on its
 launch stream; `cpu_baseline` is the CPU oracle (torch-CPU restatement of the
 reference forward + C peaks/NMS) on a bounded sample, rank 0, N=1 only.
@@ -265,11 +273,46 @@ def guard_fracs(obj, path="", hits=None):
     return hits
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(dirname: str, L, Bx, R):
+    """What the last timed step returned, as float32 .npy files: per image the
+    kept logits [n,2], boxes [n,4] and reference points [n,2], the images'
+    rows one after another (logits.npy, boxes.npy, refs.npy), and the rows per
+    image (counts.npy).  Above DUMP_MAX_BYTES a fixed, seeded sample of the
+    rows is written instead, with the rows' indices in sample_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    counts = np.array([int(x.shape[0]) for x in L], np.float32)
+    n = int(counts.sum())
+    arrs = {}
+    for name, xs in (("logits", L), ("boxes", Bx), ("refs", R)):
+        arrs[name] = np.concatenate([x.detach().float().cpu().numpy().reshape(x.shape[0], int(np.prod(x.shape[1:])))
+                                     for x in xs])
+        assert arrs[name].shape[0] == n, (name, arrs[name].shape, n)
+    row_bytes = sum(4 * v.shape[1] for v in arrs.values()) + 8  # + the row's index (float64) when sampled
+    keep = (DUMP_MAX_BYTES - counts.nbytes - 4096) // row_bytes  # 4096: the .npy headers
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrs = {k: v[rows] for k, v in arrs.items()}
+        arrs["sample_rows"] = rows.astype(np.float64)
+    arrs["counts"] = counts
+    for name, v in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy "
+                         "(rank 0; float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the kernels' HIP-event times and roofline "
+                         "fractions, the per-template-class correlation launches, the PMC and "
+                         "bare-loop records and the CPU baseline")
     ap.add_argument("--config", default="B", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step")
     ap.add_argument("--exemplars", type=int, default=None)
@@ -280,8 +323,8 @@ def main():
                          "the reference's per-exemplar module calls (demo.py:106-130)")
     ap.add_argument("--no-graphs", action="store_true",
                     help="detect path: never replay the forward as a HIP graph (TMREngine.use_graphs)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: bound of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--dist", action="store_true",
                     help="initialise torch.distributed and run the reducer exchange even at one rank "
                          "(RCCL at world 1 on a 1-GPU box exercises the N>1 code path)")
@@ -289,6 +332,8 @@ def main():
                     help="skip the per-template-class correlation launches after the timed region "
                          "(PMC passes: one launch per kernel role)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # the committed PMC records describe each config's own workload only
     own_options = (a.batch is None and a.exemplars is None and a.precision is None
                    and a.path == "detect")
@@ -337,7 +382,7 @@ def main():
         dummy = {"regression_ablation_b": False, "regression_ablation_c": False}
 
         def step():
-            out = []
+            out = ([], [], [])
             with torch.no_grad():
                 for b in range(B):
                     image = feats_d[b:b + 1]
@@ -350,9 +395,10 @@ def main():
                         po, preg, _, _ = model(image, exemplar)
                         _l, _b, _r = tmr.Get_pred_boxes(po, preg, exemplar, dummy, cfg["cls"], True)
                         pl.append(_l[0]); pb.append(_b[0]); pr.append(_r[0])
-                    L_, _, _ = tmr.NMS([torch.concat(pl)], [torch.concat(pb)], [torch.concat(pr)],
-                                       cfg["iou"])
-                    out.append(L_[0])
+                    kept_ = tmr.NMS([torch.concat(pl)], [torch.concat(pb)], [torch.concat(pr)],
+                                    cfg["iou"])
+                    for o_, k_ in zip(out, kept_):
+                        o_.append(k_[0])
             return out
     else:
         def step():
@@ -360,12 +406,12 @@ def main():
             if use_dist:
                 counts, rows = driver.pack_rows(L, Bx, R)
                 driver.all_gather_detections(counts, rows)
-            return L
+            return L, Bx, R
 
     # detect path at small batches and the module path: the forward is
     # replayed as a HIP graph once its signature recurs (TMREngine.use_graphs); a replay records no
-    # per-kernel events, so the kernels' HIP-event times then come from one
-    # eager step after the timed loop (same kernels, same stream)
+    # per-kernel events, so with --full the kernels' HIP-event times then come
+    # from one eager step after the timed loop (same kernels, same stream)
     eng.use_graphs = not a.no_graphs
     if a.path == "module":  # the module's engine replays each exemplar's forward
         model.engine().use_graphs = not a.no_graphs
@@ -377,7 +423,7 @@ def main():
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
-    if not graphs:
+    if a.full and not graphs:
         eng.decoder_events = []
         eng.xcorr_events = []
         eng.xcorr_split_events = []
@@ -394,24 +440,28 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     graph_mode = eng.last_graph if graphs else None
-    if graphs:  # the kernels' event times: one eager step after the timed loop
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *last)
+    if a.full and graphs:  # the kernels' event times: one eager step after the timed loop
         eng.decoder_events, eng.xcorr_events, eng.xcorr_split_events = [], [], []
         step()
         torch.cuda.synchronize()
-    dec_ms = [s.elapsed_time(e) for s, e in eng.decoder_events]
-    xc_ms = [s.elapsed_time(e) for s, e in eng.xcorr_events]
-    xs_ms = [s.elapsed_time(e) for s, e in eng.xcorr_split_events]
+    if a.full:
+        dec_ms = [s.elapsed_time(e) for s, e in eng.decoder_events]
+        xc_ms = [s.elapsed_time(e) for s, e in eng.xcorr_events]
+        xs_ms = [s.elapsed_time(e) for s, e in eng.xcorr_split_events]
     eng.decoder_events = eng.xcorr_events = None
-    kept = [int(x.shape[0]) for x in last]
+    kept = [int(x.shape[0]) for x in last[0]]
     phys = physical_gpus(world, dev) if use_dist else 1
+    ms_step = 1e3 * elapsed / a.steps
+    value = world * B / (elapsed / a.steps)
 
-    if rank == 0:
-        ms_step = 1e3 * elapsed / a.steps
-        value = world * B / (elapsed / a.steps)
+    def full_report(out):
+        """--full, rank 0: the roofline objects, the bare-loop record and the
+        CPU baseline, added to the result line."""
         flops = eng.last_decoder_flops  # executed FLOPs of the timed launch
         avg_s = float(np.mean(dec_ms)) / 1e3
         achieved = flops / avg_s / 1e12
-        algo = eng.last_decoder_algo
         terms = SPLIT_TERMS[prec]
         peak = F16_PEAK_TFLOPS
         kernel_name = ("tmr_split_conv heads (direct implicit-GEMM decoder_b+decoder_o f_TM half "
@@ -452,18 +502,7 @@ def main():
         if pmc_xc and pmc_xc.get("kernel_names") and not any(
                 ("rows" if eng.last_xcorr_algo == "valu" else "mfma") in n for n in pmc_xc["kernel_names"]):
             pmc_xc, why_xc = None, "the PMC run measured the other correlation kernel"
-        out = {
-            "metric": METRIC, "value": round(value, 3), "unit": "images/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if prec == "bf16" else ("fp16" if prec == "f16" else "fp32"),
-            "data": "synthetic (portable-PRNG SAM-like features, reference-init weights)",
-            "config": {"workload": cfg["desc"], "config": a.config,
-                       "images_per_gpu": B, "exemplars": E, "feature": [CIN, H // 2, W // 2],
-                       "matching_map": [EMB, H, W], "parallelism": f"dp{world}",
-                       "mean_kept_per_image": round(float(np.mean(kept)), 1),
-                       "decoder": algo, "decoder_precision": prec, "path": a.path,
-                       "hip_graph": graph_mode},
+        out.update({
             "roofline": {"bound": "mfma", "kernel": kernel_name,
                          "achieved": round(alg_achieved, 2), "peak": peak,
                          "unit": "TFLOP/s", "frac": round(alg_achieved / peak, 4),
@@ -495,7 +534,7 @@ def main():
                                            else "per unit")),
                          "path_reference_tflop_per_step": round(path_ref / 1e12, 2),
                          "path_reference_equiv_frac": round(path_ref / (ms_step / 1e3) / 1e12 / peak, 4)},
-        }
+        })
         # the correlation kernel (SURVEY.md 8d "kernel 2"): HBM-bound for small
         # templates, VALU-bound for k >= 11; both fractions, algorithmic work
         xs = float(np.mean(xc_ms)) / 1e3
@@ -549,6 +588,23 @@ def main():
             out["cpu_baseline"] = cpu_baseline(P, feats, ex, a.cpu_seconds, cfg["cls"], cfg["iou"])
         else:
             out["cpu_baseline"] = None
+
+    if rank == 0:
+        out = {
+            "metric": METRIC, "value": round(value, 3), "unit": "images/s", "n_gpus": world,
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16" if prec == "bf16" else ("fp16" if prec == "f16" else "fp32"),
+            "data": "synthetic (portable-PRNG SAM-like features, reference-init weights)",
+            "config": {"workload": cfg["desc"], "config": a.config,
+                       "images_per_gpu": B, "exemplars": E, "feature": [CIN, H // 2, W // 2],
+                       "matching_map": [EMB, H, W], "parallelism": f"dp{world}",
+                       "mean_kept_per_image": round(float(np.mean(kept)), 1),
+                       "decoder": eng.last_decoder_algo, "decoder_precision": prec, "path": a.path,
+                       "hip_graph": graph_mode},
+        }
+        if a.full:
+            full_report(out)
         out["physical_gpus"] = phys
         out["exchange"] = (f"{dist.get_backend()} all-gather of counts + kept rows per step"
                            if use_dist else "none (one process)")

@@ -1,7 +1,9 @@
 """bench.py's rank launcher (CPU): `python bench.py --gpus N` outside a
 torch.distributed launch must start N rank processes (one per GPU, the
 reference's Lightning DDP over all devices, main.py:108-119) before anything
-touches the GPU; under torchrun, WORLD_SIZE must equal --gpus."""
+touches the GPU; under torchrun, WORLD_SIZE must equal --gpus.  Also the
+benchmark's own helpers (PMC records, --dump-outputs) and, on the GPU, what a
+plain run prints and writes."""
 import importlib.util
 import os
 import subprocess
@@ -121,6 +123,81 @@ def test_committed_pmc_records_match_this_tree():
                 stale.append(f"{cfg}/{role}")
     assert set(d["configs"]) >= {"A", "B", "C", "D", "E"}
     assert not stale, f"PMC records from other kernel sources: {stale} (re-run profiles/gpu_pmc.sh)"
+
+
+def _detections(counts, seed=3):
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    L = [torch.rand(n, 2, generator=g) for n in counts]
+    Bx = [torch.rand(n, 4, generator=g) for n in counts]
+    R = [torch.rand(n, 2, generator=g) for n in counts]
+    return L, Bx, R
+
+
+def test_dump_outputs_writes_the_detections(tmp_path):
+    """--dump-outputs: the per-image lists of the last step, image after image,
+    as float32 .npy files with the rows per image beside them."""
+    import numpy as np
+    import torch
+    b = _bench()
+    counts = [5, 0, 7]
+    L, Bx, R = _detections(counts)
+    d = tmp_path / "out" / "dir"  # created on demand
+    b.dump_outputs(str(d), L, Bx, R)
+    assert sorted(os.listdir(d)) == ["boxes.npy", "counts.npy", "logits.npy", "refs.npy"]
+    got = {n: np.load(d / (n + ".npy")) for n in ("logits", "boxes", "refs", "counts")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["counts"].tolist() == counts
+    assert got["logits"].shape == (12, 2) and got["boxes"].shape == (12, 4) and got["refs"].shape == (12, 2)
+    assert np.array_equal(got["logits"], torch.cat(L).numpy())
+    assert np.array_equal(got["boxes"], torch.cat(Bx).numpy())
+    assert np.array_equal(got["refs"], torch.cat(R).numpy())
+
+
+def test_dump_outputs_samples_above_the_size_limit(tmp_path, monkeypatch):
+    """Above the limit the same seeded sample of rows is written every time,
+    with the rows' indices, and the files together stay under the limit."""
+    import numpy as np
+    import torch
+    b = _bench()
+    L, Bx, R = _detections([300, 500])
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 16384)
+    for name in ("a", "b"):
+        b.dump_outputs(str(tmp_path / name), L, Bx, R)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["boxes.npy", "counts.npy", "logits.npy", "refs.npy", "sample_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 16384
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 800 and np.all(np.diff(rows) > 0)
+    assert np.load(tmp_path / "a" / "counts.npy").tolist() == [300, 500]  # of the whole output
+    assert np.array_equal(np.load(tmp_path / "a" / "boxes.npy"), torch.cat(Bx).numpy()[rows.astype(int)])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times N steps and
+    prints the headline fields only (nothing that needs a run of its own);
+    --dump-outputs writes the last step's detections."""
+    import json
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2",
+                        "--warmup", "1", "--config", "A", "--dump-outputs", str(tmp_path / "o")],
+                       capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "images/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "fp32" and out["metric"]
+    assert out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(1e3 / out["ms_per_step"], rel=1e-3)  # config A: one image per step
+    for k in ("roofline", "roofline_xcorr", "bare_loop", "cpu_baseline"):
+        assert k not in out
+    counts = np.load(tmp_path / "o" / "counts.npy")
+    boxes = np.load(tmp_path / "o" / "boxes.npy")
+    assert counts.shape == (1,) and counts[0] >= 1 and boxes.shape == (int(counts[0]), 4)
+    assert out["config"]["mean_kept_per_image"] == round(float(counts.mean()), 1)
+    assert np.isfinite(boxes).all() and np.load(tmp_path / "o" / "logits.npy").shape == (int(counts[0]), 2)
 
 
 def test_frac_guard_nulls_fractions_above_one():

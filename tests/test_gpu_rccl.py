@@ -48,7 +48,7 @@ def test_bench_dist_path_rccl_world1():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
            "--gpus", "1", "--dist", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--no-cpu-baseline", "--no-xcorr-classes"]
+           "--full", "--no-cpu-baseline", "--no-xcorr-classes"]
     p = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=300, cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -56,3 +56,6 @@ def test_bench_dist_path_rccl_world1():
     assert out["n_gpus"] == 1 and out["physical_gpus"] == 1
     assert out["exchange"].startswith("nccl all-gather")
     assert out["value"] > 0
+    # --full: the kernels' HIP-event figures are on the line, the skipped legs are not
+    assert out["roofline"]["avg_launch_ms"] > 0 and out["roofline_xcorr"]["avg_launch_ms"] > 0
+    assert out["cpu_baseline"] is None and "by_class" not in out["roofline_xcorr"]
