@@ -184,7 +184,9 @@ int tmr_template_split(const float *templates, const tmr_unit_t *units, int U, i
  * the tiles and adds the head biases.  Size: TMR_SIZE_HEADS_PARTIALS floats. */
 /* o [U,1,H,W] = head_bias[4] + sum_t partials[t][4];  b [U,4,H,W] (nullable) =
  * head_bias[j] + sum_t partials[t][j], t over ceil(N/tile_n) channel tiles
- * (tile_n = 128, the split kernel's tile; 64 is accepted too). */
+ * (tile_n = 128, the split kernel's tile; 64 is accepted too).  With b NULL
+ * only the objectness partials (j = 4) are read.  Over a tile window of a
+ * launch (TMR_SPLIT_TILE_WINDOW): partials + first * 5*U*H*W, N = 128 * count. */
 int tmr_heads_reduce(const float *partials, int N, int tile_n, int U, int H, int W,
                      const float *head_bias, float *o, float *b, void *stream);
 
@@ -285,12 +287,48 @@ int tmr_split_wpack(const float *w, int N, int C0, int C1, int ks, int prec, con
  * back to back (image-major order; 0 or 1: unit-major).  Results are the
  * same either way; only the order, and so the cache reuse, changes. */
 #define TMR_SPLIT_UNITS_PER_IMAGE_SHIFT 8
+/* flags bits 16..23 / 24..30: a window (first tile, tile count) of the
+ * ceil(N/128) 128-channel tiles: the launch computes only those tiles, from
+ * the same packs, acc_init slabs and out / partials layout as the full launch
+ * (N, bias, headw stay the full problem's), so what it writes is bit-identical
+ * to the full launch's; count 0 (with first 0) = every tile.  Head partials
+ * are [tile][5][U][H][W], so tmr_heads_reduce over a window takes partials +
+ * first * 5 * U * H * W and N = 128 * count (b = NULL where the window holds
+ * no regression channels).  A head's partial from a tile where its head
+ * weights are zero is 0 * act = +-0 (act finite): leaving such tiles out
+ * changes at most the sign of an exactly zero sum, and never a sum the
+ * reduce starts from +0. */
+#define TMR_SPLIT_TILE_FIRST_SHIFT 16
+#define TMR_SPLIT_TILE_COUNT_SHIFT 24
+#define TMR_SPLIT_TILE_WINDOW(first, count) \
+    (((first) << TMR_SPLIT_TILE_FIRST_SHIFT) | ((count) << TMR_SPLIT_TILE_COUNT_SHIFT))
 /* out[s][p] = max_c |x[s][c][p]| for x [S][C][HW] */
 int tmr_pixel_absmax(const float *x, int S, int C, int64_t HW, float *out, void *stream);
 int tmr_split_conv(const void *xp0, int C0, const int32_t *unit_image, const void *xp1, int C1, int U,
                    int H, int W, int ks, int prec, const void *wpack, const float *wmax, const float *xmax,
                    const float *bias, int N, int leaky, const float *headw, const float *acc_init,
                    float *out, int flags, void *stream);
+
+/* tmr_split_conv_points: the heads launch at a list of points.  For every
+ * candidate listed by `tiles` it computes what tmr_split_conv (headw given,
+ * the same operands and flags) followed by tmr_heads_reduce writes into
+ * b [U][4][H][W] at that candidate's pixel -- bit for bit: the same chain of
+ * MFMAs per accumulator element, head arithmetic and tile-order sum -- and
+ * writes those four values there; every other element of b is left untouched.
+ * tiles (device int32[ntiles][3]): (unit, first candidate, count), count in
+ * 1..TMR_POINTS_TILE, a tile within one unit; candidate i of unit u has its
+ * pixel index y*W + x in ((const int32_t *)box)[4 * (u*H*W + i)], where
+ * tmr_peaks_decode with TMR_PEAKS_FIND_ONLY leaves it.  acc_init is NULL or
+ * tiled (TMR_SPLIT_TILED_INIT, optionally _INIT_BCAST / _INIT_BF16); the
+ * flags' tile window selects the channel tiles summed into b (at most 8, e.g.
+ * decoder_b's of decoder_b || decoder_o).  ks must be 3; other kernel sizes
+ * and wider windows return TMR_E_UNSUPPORTED (run the dense window instead). */
+#define TMR_POINTS_TILE 64
+int tmr_split_conv_points(const void *xp0, int C0, const int32_t *unit_image, const void *xp1, int C1, int U,
+                          int H, int W, int ks, int prec, const void *wpack, const float *wmax, const float *xmax,
+                          const float *bias, int N, int leaky, const float *headw, const float *head_bias,
+                          const float *acc_init, const float *box, const int32_t *tiles, int ntiles, float *b,
+                          int flags, void *stream);
 
 /* ---- (a16) custom_shape_3x3_maxpool2d -----------------------------------
  * utils/TM_utils.py:337-361 on device fp32 planes x [planes][H][W]: out[e] =
@@ -318,6 +356,15 @@ int tmr_maxpool3x3(const float *x, int64_t planes, int H, int W, int mask9, floa
  * inputs, where it is the other neighbour, as the reference's torch.exp (MKL
  * vsExp) rounds; NULL = correctly rounded everywhere. */
 #define TMR_PEAKS_PROB_SCRATCH 2  /* input_is_prob flag: prob is scratch (see above) */
+/* Two-phase use (input_is_prob flags; value 4 is not a flag and is refused).
+ * TMR_PEAKS_FIND_ONLY: probability map + finder only (reg may be NULL):
+ * logits, ref and counts as above, and box row i of unit u holds candidate
+ * i's pixel index y*W + x as an int32 in its first element instead of a box
+ * (the dummy row of an empty unit is written as above).
+ * TMR_PEAKS_DECODE_ONLY: the decode alone over the rows a FIND_ONLY call left
+ * (o, prob, logits unused but required non-NULL): box rows become boxes. */
+#define TMR_PEAKS_FIND_ONLY 8
+#define TMR_PEAKS_DECODE_ONLY 16
 int tmr_peaks_decode(const float *o, int input_is_prob, const float *reg, int U, int H, int W,
                      const tmr_peak_param_t *params, float *prob, float *logits, float *box,
                      float *ref, int32_t *counts, const void *exp_table, void *stream);

@@ -48,6 +48,10 @@ SPLIT_XMAX_PER_UNIT = 32  # xmax is float[U]: one activation scale per unit / ou
 SPLIT_XMAX_PER_PIXEL = 64  # 1x1 stores: xmax is float[U][H][W], one scale per output pixel
 PEAKS_PROB_SCRATCH = 2  # tmr_peaks_decode: prob is scratch (low logits hold -1)
 SPLIT_UNITS_PER_IMAGE_SHIFT = 8  # flags bits 8..15: E units per image -> image-major heads order
+# flags bits 16..23 / 24..30: the launch's window (first, count) of 128-channel tiles; 0/0 = all
+SPLIT_TILE_FIRST_SHIFT, SPLIT_TILE_COUNT_SHIFT = 16, 24
+PEAKS_FIND_ONLY, PEAKS_DECODE_ONLY = 8, 16  # tmr_peaks_decode: the finder alone / the decode alone
+POINTS_TILE = 64  # TMR_POINTS_TILE: candidates per tile of tmr_split_conv_points
 # correlation kernel choice (tmr_xcorr_args_t.algo)
 XCORR_ALGOS = {"auto": 0, "valu": 1, "mfma": 2}
 XPACK_UPSAMPLE, XPACK_ONES = 1, 2  # tmr_split_xpack `up` bits
@@ -90,6 +94,8 @@ SIGNATURES = {
     "tmr_split_wpack": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "tmr_split_conv": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I,
                             _P]),
+    "tmr_split_conv_points": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P,
+                                   _P, _P, _I, _P, _I, _P]),
     "tmr_peaks_decode": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tmr_maxpool3x3": (_I, [_P, _L, _I, _I, _I, _P, _P]),
     "tmr_nms": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _D, _P, _P, _P, _P, _P, _P, _P]),
@@ -125,6 +131,18 @@ def load() -> ctypes.CDLL:
             raise TMRError("libtmr.so ABI version mismatch")
         _lib = lib
         return lib
+
+
+def split_tile_window(first: int, count: int) -> int:
+    """TMR_SPLIT_TILE_WINDOW: the flags bits of a channel-tile window (0, 0 = every tile)."""
+    if not (0 <= first < 256 and 0 <= count < 128):
+        raise TMRError("tile window out of range")
+    return (first << SPLIT_TILE_FIRST_SHIFT) | (count << SPLIT_TILE_COUNT_SHIFT)
+
+
+def split_tile_window_of(flags: int):
+    """(first, count) of a flags word's tile window."""
+    return (flags >> SPLIT_TILE_FIRST_SHIFT) & 0xff, (flags >> SPLIT_TILE_COUNT_SHIFT) & 0x7f
 
 
 def check(rc: int, what: str = "") -> None:

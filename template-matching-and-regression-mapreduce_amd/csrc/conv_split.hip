@@ -152,6 +152,12 @@ __device__ __forceinline__ void buffer_lds16(__amdgpu_buffer_rsrc_t r, lds_ptr_t
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
 }
 
+// 16-B load through a buffer descriptor into registers
+template <typename V>
+__device__ __forceinline__ V buffer_load16(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
+}
+
 __device__ __forceinline__ f32x4 mma(h8 a, h8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
@@ -221,7 +227,38 @@ struct SArgs {
     int NC0, NC1, U, H, W, N, NT, MT, TXN, Hp, Wp, Npad, leaky;
     int flags;  // TMR_SPLIT_TILED_OUT / TMR_SPLIT_TILED_INIT
     int EI;     // units per image of the image-major block order (1: unit-major)
+    int NT0, NTW;  // channel-tile window of this launch: tiles NT0 .. NT0 + NTW - 1 of the NT
 };
+
+// s_x s_w of unit u: the exact power of two between the accumulator's units
+// and the result's.  Activation scale: one per launch, or per unit / output
+// slab u (TMR_SPLIT_XMAX_PER_UNIT: a unit's precision then does not depend on
+// the magnitudes of the other units in the batch); TMR_SPLIT_XMAX_PER_PIXEL:
+// the epilogue undoes a scale per output pixel.
+template <int PREC>
+__device__ __forceinline__ float split_sxw(const SArgs &a, int u) {
+    const float *xm = (a.xmax && !(a.flags & TMR_SPLIT_XMAX_PER_PIXEL))
+                          ? a.xmax + ((a.flags & TMR_SPLIT_XMAX_PER_UNIT) ? u : 0) : nullptr;
+    return Prec<PREC>::SCALED ? split_scale(xm) * split_scale(a.wmax) : 1.0f;
+}
+
+// The fused heads' arithmetic per pixel pair, shared by the dense epilogue and
+// the points kernel.  acc * inv is exact (a power of two), so fma(acc, inv,
+// bias) rounds once, like the separate multiply and add; LeakyReLU as
+// max(v, 0.01 v) (= the select form for every v, incl. -0, inf and NaN).
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 head_act(f2 acc, f2 inv2, f2 bn2, int leaky) {
+    f2 v = __builtin_elementwise_fma(acc, inv2, bn2);
+    if (leaky) {
+        const f2 m = v * (f2){0.01f, 0.01f};
+        v = (f2){fmaxf(v.x, m.x), fmaxf(v.y, m.y)};
+    }
+    return v;
+}
+__device__ __forceinline__ void head_fma(f2 v, const f2 (&hw2)[NHEAD], f2 (&hs)[NHEAD]) {
+#pragma unroll
+    for (int k = 0; k < NHEAD; ++k) hs[k] = __builtin_elementwise_fma(v, hw2[k], hs[k]);
+}
 
 template <int KS, int PREC>
 struct Geo {
@@ -329,24 +366,25 @@ __global__ __launch_bounds__(NTHREADS) void split_conv_kernel(SArgs a) {
         // image-major (TMR_SPLIT_UNITS_PER_IMAGE): an image's EI units innermost,
         // so its units' blocks at one tile run back to back on one XCD
         // (measured, profiles/r05c: config-B heads launch 106.55 -> 105.96 ms)
-        const int per_unit = a.NT * a.MT;
+        const int per_unit = a.NTW * a.MT;
         const int ub = L / (a.EI * per_unit), rr = L - ub * a.EI * per_unit;
         u = ub * a.EI + rr % a.EI;
         const int r = rr / a.EI;
-        if (a.MT % PXG == 0 && a.NT % NG == 0) {
+        if (a.MT % PXG == 0 && a.NTW % NG == 0) {
             // pixel tiles in groups of 8; for each group the channel tiles in
             // groups of 4: the 32 co-resident blocks of an XCD share 4 weight
             // slabs and 8 halos through its L2, and a group's halos stay
             // there while its 4 channel groups pass
-            const int gsz = PXG * a.NT;
+            const int gsz = PXG * a.NTW;
             const int pg = r / gsz, r2 = r - pg * gsz;
             const int ng = r2 / (PXG * NG), r3 = r2 - ng * (PXG * NG);
             mt = pg * PXG + r3 / NG;
             nt = ng * NG + r3 % NG;
         } else {
-            nt = r % a.NT;
-            mt = r / a.NT;
+            nt = r % a.NTW;
+            mt = r / a.NTW;
         }
+        nt += a.NT0;
     }
     const int ty0 = (mt / a.TXN) * TH, tx0 = (mt % a.TXN) * TW;
     const int img = a.unit_image ? a.unit_image[u] : u;
@@ -429,13 +467,7 @@ __global__ __launch_bounds__(NTHREADS) void split_conv_kernel(SArgs a) {
     // the exact power of two s_x s_w); masked elements read a clamped legal
     // address and are zeroed by a select, never by a branch around the load.
     // 16x16 accumulator: column = pixel l16, row = n 4*kg + r.
-    // activation scale: one per launch, or per unit / output slab u
-    // (TMR_SPLIT_XMAX_PER_UNIT: a unit's precision then does not depend on
-    // the magnitudes of the other units in the batch)
-    // (TMR_SPLIT_XMAX_PER_PIXEL: the epilogue undoes a scale per output pixel)
-    const float *xm = (a.xmax && !(a.flags & TMR_SPLIT_XMAX_PER_PIXEL))
-                          ? a.xmax + ((a.flags & TMR_SPLIT_XMAX_PER_UNIT) ? u : 0) : nullptr;
-    const float sxw = PR::SCALED ? split_scale(xm) * split_scale(a.wmax) : 1.0f;
+    const float sxw = split_sxw<PREC>(a, u);
     const int HW = a.H * a.W;
     f32x4 acc[NIN][8];
     // tiled acc layout: [slab][nt][mt][wave][in*8+jp][lane][4] fp32 (bf16
@@ -703,11 +735,7 @@ __global__ __launch_bounds__(NTHREADS) void split_conv_kernel(SArgs a) {
             }
         return;
     }
-    // Heads: per pixel pair (jp = 2q, 2q+1) on v_pk_fma_f32.  acc * inv is
-    // exact (a power of two), so fma(acc, inv, bias) rounds once, like the
-    // separate multiply and add; LeakyReLU as max(v, 0.01 v) (= the select
-    // form for every v, incl. -0, inf and NaN).
-    typedef float f2 __attribute__((ext_vector_type(2)));
+    // Heads: per pixel pair (jp = 2q, 2q+1) on v_pk_fma_f32 (head_act, head_fma)
     f2 hs2[4][NHEAD];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -724,16 +752,8 @@ __global__ __launch_bounds__(NTHREADS) void split_conv_kernel(SArgs a) {
 #pragma unroll
             for (int k = 0; k < NHEAD; ++k) hw2[k] = (f2){shw[nl * NHEAD + k], shw[nl * NHEAD + k]};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f2 v = {acc[in][2 * q][r], acc[in][2 * q + 1][r]};
-                v = __builtin_elementwise_fma(v, inv2, bn2);
-                if (a.leaky) {
-                    const f2 m = v * (f2){0.01f, 0.01f};
-                    v = (f2){fmaxf(v.x, m.x), fmaxf(v.y, m.y)};
-                }
-#pragma unroll
-                for (int k = 0; k < NHEAD; ++k) hs2[q][k] = __builtin_elementwise_fma(v, hw2[k], hs2[q][k]);
-            }
+            for (int q = 0; q < 4; ++q)
+                head_fma(head_act((f2){acc[in][2 * q][r], acc[in][2 * q + 1][r]}, inv2, bn2, a.leaky), hw2, hs2[q]);
             // keep the LDS reads of bias / head weights per row (hoisted, they
             // would overlap the 128 live accumulators)
             __builtin_amdgcn_sched_barrier(0);
@@ -792,7 +812,7 @@ int launch_split(SArgs a, hipStream_t s) {
     if (tmr_set_max_lds((const void *)kern, lds) !=
         hipSuccess)
         return TMR_E_HIP;
-    const int64_t blocks = (int64_t)a.NT * a.MT * a.U;
+    const int64_t blocks = (int64_t)a.NTW * a.MT * a.U;
     if (blocks <= 0) return TMR_OK;
     TMR_REQUIRE(blocks < (1ll << 31));
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NTHREADS), lds, s, a);
@@ -821,12 +841,303 @@ int dispatch_ks(int ks, int prec, const SArgs &a, hipStream_t s) {
     }
 }
 
+// ---------------------------------------------------------------- points
+// The same conv + heads at a list of (unit, pixel) points: one block per tile
+// of up to PT points of ONE unit x up to NWAVES 128-channel tiles, wave w
+// owning channel tile NT0 + w (8 n fragments x PT / 16 point columns = the
+// dense wave's 128 accumulator registers).  The MFMA's B operand is the
+// points' gathered records (a record is one K = 32 slice; the records'
+// zero-padded halo makes every 3x3 neighbour a legal address), its A operand
+// the dense kernel's weight records.  The tile's gathered 3x3 records of a
+// half-chunk are staged in LDS once (LDS-DMA, one half-chunk ahead, two
+// buffers) and read by all waves; each wave streams its own weight fragments
+// from L2 into registers one (tap, term) stage ahead of the MFMAs.  (Every
+// wave gathering its own B fragments from L2 -- 64 cache lines per load, 8x
+// redundant -- ran the config-B launch in 15.1 ms.)  Every output element
+// is the dense kernel's chain: acc_init * s_x s_w, then per chunk the hi
+// half-chunk's wh.xh, wl.xh per tap and the lo half-chunk's wh.xl per tap,
+// head_act / head_fma over the tile's channels in the dense lane order, the
+// lane groups as (x0 + x1) + (x2 + x3), the two 64-channel halves, then the
+// tiles in order and the head bias (heads_reduce_kernel).  MFMA columns are
+// independent, so a point's value does not depend on its tile mates.
+constexpr int PT = TMR_POINTS_TILE;
+constexpr int PCG = PT / 16;  // 16-point column groups
+static_assert(PT == 64 && 4 * PT <= NTHREADS, "points tile: one gather lane per point");
+
+struct PArgs {
+    SArgs s;
+    const float *head_bias;
+    const float *box;       // the finder's rows: pixel index in ((int *)box)[4 * (u * HW + i)]
+    const int32_t *tiles;   // [ntiles][3]: unit, first candidate, count (1..PT)
+    float *b;               // [U][4][H][W], written at the points only
+};
+
+template <int KS, int PREC>
+__global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
+    typedef Prec<PREC> PR;
+    typedef typename PR::V V;
+    constexpr int T = KS * KS, HALVES = PR::HALVES, WREC = PR::WREC;
+    constexpr int NF = BM / 16;                       // n fragments per tile
+    constexpr int NS = HALVES == 2 ? 3 * T : T;       // (tap, term) stages per chunk
+    const SArgs &a = pa.s;
+    // LDS: the tile's gathered B records of one half-chunk, [tap][piece][point]
+    // 16-B slots (the dense halo's piece planes: a fragment read takes 16
+    // consecutive slots of one plane), two buffers; then the tiles' head sums
+    constexpr int BB = T * P * PT * 16;  // bytes per B buffer
+    extern __shared__ __attribute__((aligned(16))) char plds[];
+    char *Bs = plds;
+    float(*red)[4][PT] = reinterpret_cast<float(*)[4][PT]>(plds + 2 * BB);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l16 = lane & 15, kg = lane >> 4;
+    const int HW = a.H * a.W;
+    const int32_t *tl = pa.tiles + 3 * (size_t)blockIdx.x;
+    const int u = min(max(tl[0], 0), a.U - 1);
+    const int first = min(max(tl[1], 0), HW - 1), cnt = min(max(tl[2], 0), PT);
+    const int img = a.unit_image ? a.unit_image[u] : u;
+    const int NC = a.NC0 + a.NC1;
+    // a wave past the window's tiles repeats its first tile (it shares the
+    // gathers and the barriers) and stores nothing
+    const bool active = wave < a.NTW;
+    const int nt = a.NT0 + (active ? wave : 0);
+    const int *pixi = reinterpret_cast<const int *>(pa.box) + 4 * (size_t)u * HW;
+    // point p's pixel (a point past the tile's count repeats a legal candidate
+    // row and is never stored; a pixel index is clamped into the map, so no
+    // gather leaves the padded plane)
+    auto pixel = [&](int p) { return min(max(pixi[4 * (size_t)min(first + (p < cnt ? p : 0), HW - 1)], 0), HW - 1); };
+
+    {
+        // this lane's point of each column group
+        int py[PCG], px[PCG];
+#pragma unroll
+        for (int j = 0; j < PCG; ++j) {
+            const int pix = pixel(j * 16 + l16);
+            py[j] = pix / a.W;
+            px[j] = pix - py[j] * a.W;
+        }
+        // operands through buffer descriptors (SGPRs): every load is base +
+        // uniform soffset + a 32-bit per-lane voffset (+ an immediate), so the
+        // loop holds two address registers per lane, and the range check
+        // turns a stray read into zeros instead of a fault
+        const uint32_t cstride = (uint32_t)a.Hp * a.Wp * XREC;
+        const int h0 = a.NC0 * HALVES, h1 = a.NC1 * HALVES;
+        const __amdgpu_buffer_rsrc_t xr0 = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(h0 ? a.x0 + (size_t)img * h0 * cstride : a.x1), (short)0, h0 * cstride, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr1 = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(h1 ? a.x1 + (size_t)u * h1 * cstride : a.x0), (short)0, h1 * cstride, 0x00020000);
+        const uint32_t tapstride = (uint32_t)NC * a.Npad * WREC;
+        const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)a.wp, (short)0, T * tapstride, 0x00020000);
+        const uint32_t aoff = (uint32_t)kg * a.Npad * 16 + ((uint32_t)nt * BM + l16) * 16;
+        // The gather of half-chunk hc into buffer hc & 1 by LDS-DMA: wave
+        // instruction i = tap * 4 + piece fills that plane's PT slots, lane =
+        // point (its record's piece: 16 B), the instructions dealt round robin
+        // to the waves.  Issued at the start of half-chunk hc - 1 (the buffer
+        // was last read in hc - 2, before the barrier that ended it) and
+        // complete before the barrier that ends hc - 1.
+        uint32_t goff;
+        {
+            const int pix = pixel(lane), y = pix / a.W;
+            goff = (uint32_t)(y * a.Wp + (pix - y * a.W)) * 16;
+        }
+        const uint32_t qstride = (uint32_t)a.Hp * a.Wp * 16;
+        auto gather = [&](int hc) {
+            const bool s0 = hc < h0;
+            const uint32_t hs_ = (uint32_t)(s0 ? hc : hc - h0) * cstride;
+#pragma unroll
+            for (int m = 0; m < (T * P + NWAVES - 1) / NWAVES; ++m) {
+                const int i = wave + NWAVES * m;
+                if (i < T * P) {
+                    const int tap = i / P, q = i % P, ky = tap / KS, kx = tap % KS;
+                    buffer_lds16(s0 ? xr0 : xr1, (lds_ptr_t)(Bs + (hc & 1) * BB + i * (PT * 16)), goff,
+                                 hs_ + q * qstride + (uint32_t)(ky * a.Wp + kx) * 16);
+                }
+            }
+        };
+        const int bfo = kg * (PT * 16) + l16 * 16;  // this lane's slot of a (tap, column group 0) fragment
+        auto bfrag = [&](int hc, int tap, int j) -> V {
+            return *reinterpret_cast<const V *>(Bs + (hc & 1) * BB + tap * (P * PT * 16) + bfo + j * 256);
+        };
+        gather(0);
+
+        const float sxw = split_sxw<PREC>(a, u);
+        f32x4 acc[NF][PCG];
+        if (a.acc_init) {  // tiled (host-checked): the dense kernel's element of slab / tile / wave / lane
+            const int islab = (a.flags & TMR_SPLIT_INIT_BCAST) ? 0 : img;
+            const bool i16 = a.flags & TMR_SPLIT_INIT_BF16;
+#pragma unroll
+            for (int j = 0; j < PCG; ++j) {
+                const int mt = (py[j] / TH) * a.TXN + px[j] / TW;
+                const int wpix = (py[j] % TH) >> 2, jp = ((py[j] & 3) << 1) | ((px[j] % TW) >> 4);
+                // 16-B group index of (wave wpix * WNS, in 0): + (f / NIN) waves, + (f % NIN) * 8 groups of 64
+                const size_t g4 = (((((size_t)islab * a.NT + nt) * a.MT + mt) * NWAVES + wpix * WNS) * ACCW) / 4 +
+                                  jp * 64 + kg * 16 + (px[j] & 15);
+                if (i16) {
+                    const b4 *ai = reinterpret_cast<const b4 *>(a.acc_init) + g4;
+#pragma unroll
+                    for (int f = 0; f < NF; ++f)
+                        acc[f][j] = __builtin_convertvector(ai[(f / NIN) * (ACCW / 4) + (f % NIN) * 8 * 64], f32x4) * sxw;
+                } else {
+                    const f32x4 *ai = reinterpret_cast<const f32x4 *>(a.acc_init) + g4;
+#pragma unroll
+                    for (int f = 0; f < NF; ++f)
+                        acc[f][j] = ai[(f / NIN) * (ACCW / 4) + (f % NIN) * 8 * 64] * sxw;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+#pragma unroll
+                for (int j = 0; j < PCG; ++j) acc[f][j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        }
+
+        // stage s of a chunk: F16X3 s < 2T: hi half-chunk, tap s / 2, term s % 2
+        // (wh, wl); s >= 2T: lo half-chunk, tap s - 2T, wh.  One-term: tap s.
+        auto st_part = [](int s) { return HALVES == 2 && s >= 2 * T ? 1 : 0; };
+        auto st_tap = [](int s) { return HALVES == 2 ? (s >= 2 * T ? s - 2 * T : s / 2) : s; };
+        auto st_term = [](int s) { return HALVES == 2 && s < 2 * T ? s & 1 : 0; };
+        auto st_newb = [](int s) { return !(HALVES == 2 && s < 2 * T && (s & 1)); };
+        auto st_first = [](int s) { return s == 0 || (HALVES == 2 && s == 2 * T); };  // of a half-chunk
+        auto st_last = [](int s) { return s == NS - 1 || (HALVES == 2 && s == 2 * T - 1); };
+        V an[NF], bn[PCG];  // the next stage's fragments
+        auto load_stage = [&](int c, int s) {
+            const int tap = st_tap(s);
+            const uint32_t as = (uint32_t)tap * tapstride + (uint32_t)c * a.Npad * WREC +
+                                (uint32_t)st_term(s) * 4 * a.Npad * 16;
+#pragma unroll
+            for (int f = 0; f < NF; ++f) an[f] = buffer_load16<V>(wr, aoff + f * 256, as);
+            if (st_newb(s) && !st_first(s)) {  // (a half-chunk's first B waits for its barrier)
+#pragma unroll
+                for (int j = 0; j < PCG; ++j) bn[j] = bfrag(c * HALVES + st_part(s), tap, j);
+            }
+        };
+        load_stage(0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        V bc[PCG];
+        const int NHC = NC * HALVES;
+        for (int c = 0; c < NC; ++c) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int hc = c * HALVES + st_part(s);
+                V ac[NF];
+#pragma unroll
+                for (int f = 0; f < NF; ++f) ac[f] = an[f];
+                if (st_first(s)) {
+                    if (hc + 1 < NHC) gather(hc + 1);
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j) bc[j] = bfrag(hc, st_tap(s), j);
+                } else if (st_newb(s)) {
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j) bc[j] = bn[j];
+                }
+                // the next stage (past the end: a harmless re-read of the last chunk's first)
+                if (s + 1 < NS)
+                    load_stage(c, s + 1);
+                else
+                    load_stage(c + 1 < NC ? c + 1 : c, 0);
+                // the loads stay ahead of this stage's MFMAs and behind the last
+                // stage's (unpinned, the scheduler hoists whole chunks of loads
+                // and spills the accumulators)
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < PCG; ++j)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) acc[f][j] = mma(ac[f], bc[j], acc[f][j]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (st_last(s)) {  // the next half-chunk's gather has landed; this one's buffer is free
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __syncthreads();
+                }
+            }
+        }
+
+        // heads of this tile: lane group kg holds rows n = 16 f + 4 kg + r
+        const float inv = 1.0f / sxw;
+        const f2 inv2 = {inv, inv};
+        f2 hs[WNS][PCG / 2][NHEAD];
+#pragma unroll
+        for (int w = 0; w < WNS; ++w)
+#pragma unroll
+            for (int q = 0; q < PCG / 2; ++q)
+#pragma unroll
+                for (int k = 0; k < NHEAD; ++k) hs[w][q][k] = (f2){0.0f, 0.0f};
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = nt * BM + f * 16 + 4 * kg + r;
+                const float bv = n < a.N ? a.bias[n] : 0.0f;
+                const f2 bn2 = {bv, bv};
+                f2 hw2[NHEAD];
+#pragma unroll
+                for (int k = 0; k < NHEAD; ++k) {
+                    const float h = a.headw[(size_t)n * NHEAD + k];
+                    hw2[k] = (f2){h, h};
+                }
+#pragma unroll
+                for (int q = 0; q < PCG / 2; ++q)
+                    head_fma(head_act((f2){acc[f][2 * q][r], acc[f][2 * q + 1][r]}, inv2, bn2, a.leaky), hw2,
+                             hs[f / NIN][q]);
+            }
+        // over the lane groups, (x0 + x1) + (x2 + x3), then the two halves
+#pragma unroll
+        for (int q = 0; q < PCG / 2; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    float z[WNS];
+#pragma unroll
+                    for (int w = 0; w < WNS; ++w) {
+                        const float x = hs[w][q][k][e];
+                        const float y = x + __shfl_xor(x, 16);
+                        z[w] = y + __shfl_xor(y, 32);
+                    }
+                    if (kg == 0 && active) red[wave][k][(2 * q + e) * 16 + l16] = WNS == 2 ? z[0] + z[1] : z[0];
+                }
+    }
+    __syncthreads();
+    if (tid < 4 * PT) {
+        const int k = tid / PT, p = tid % PT;
+        if (p < cnt) {
+            const int pix = pixel(p);
+            float s = 0.0f;
+            for (int t = 0; t < a.NTW; ++t) s += red[t][k][p];
+            pa.b[((size_t)u * 4 + k) * HW + pix] = s + pa.head_bias[k];
+        }
+    }
+}
+
+template <int PREC>
+int launch_points(const PArgs &pa, int ntiles, hipStream_t s) {
+    constexpr size_t lds = 2 * 9 * P * PT * 16 + NWAVES * 4 * PT * sizeof(float);
+    auto kern = split_points_kernel<3, PREC>;
+    if (tmr_set_max_lds((const void *)kern, lds) != hipSuccess) return TMR_E_HIP;
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(NTHREADS), lds, s, pa);
+    TMR_CHECK_LAUNCH();
+    return TMR_OK;
+}
+
 inline int prec_halves(int prec) { return prec == TMR_PREC_F16X3 ? 2 : 1; }
 inline int prec_wrec(int prec) { return prec == TMR_PREC_F16X3 ? 128 : 64; }
 inline bool prec_ok(int prec) {
     return prec == TMR_PREC_F16X3 || prec == TMR_PREC_BF16 || prec == TMR_PREC_F16;
 }
 inline bool ks_ok(int ks) { return ks == 1 || ks == 3 || ks == 5 || ks == 7; }
+// the channel-tile window of `flags` (TMR_SPLIT_TILE_FIRST_SHIFT / _COUNT_SHIFT;
+// count 0 with first 0: every tile)
+inline bool tile_window(int flags, int NT, int &first, int &count) {
+    first = (flags >> TMR_SPLIT_TILE_FIRST_SHIFT) & 0xff;
+    count = (flags >> TMR_SPLIT_TILE_COUNT_SHIFT) & 0x7f;
+    if (count == 0) {
+        if (first != 0) return false;
+        count = NT;
+    }
+    return first + count <= NT;
+}
 inline int pad_h(int H, int ks) { return (int)tmr_cdiv(H, TH) * TH + ks - 1; }
 inline int pad_w(int W, int ks) { return (int)tmr_cdiv(W, TW) * TW + ks - 1; }
 
@@ -1174,6 +1485,7 @@ int split_common(const void *xp0, int C0, const int32_t *unit_image, const void 
     a.flags = flags & 0xff;
     a.EI = std::max(1, (flags >> TMR_SPLIT_UNITS_PER_IMAGE_SHIFT) & 0xff);
     TMR_REQUIRE(U % a.EI == 0);
+    TMR_REQUIRE(tile_window(flags, a.NT, a.NT0, a.NTW));
     hipStream_t s = tmr_stream(stream);
     return epi ? dispatch_ks<1>(ks, prec, a, s) : dispatch_ks<0>(ks, prec, a, s);
 }
@@ -1353,4 +1665,64 @@ extern "C" int tmr_split_conv(const void *xp0, int C0, const int32_t *unit_image
     TMR_REQUIRE(!(flags & TMR_SPLIT_TILED_OUT));  // the head partials of the fused epilogue to out
     return split_common(xp0, C0, unit_image, xp1, C1, U, H, W, ks, prec, wpack, wmax, xmax, bias, N, leaky, acc_init,
                         nullptr, headw, out, 1, flags, stream);
+}
+
+// The four regression heads at the points of `tiles` (tmr.h): the operands of
+// the dense heads launch (tmr_split_conv with headw) and, bit for bit, its +
+// tmr_heads_reduce's values of b at those pixels.  ks = 3 and at most 8
+// channel tiles (the flags' tile window); anything else is TMR_E_UNSUPPORTED
+// and belongs to the dense launch.
+extern "C" int tmr_split_conv_points(const void *xp0, int C0, const int32_t *unit_image, const void *xp1, int C1,
+                                     int U, int H, int W, int ks, int prec, const void *wpack, const float *wmax,
+                                     const float *xmax, const float *bias, int N, int leaky, const float *headw,
+                                     const float *head_bias, const float *acc_init, const float *box,
+                                     const int32_t *tiles, int ntiles, float *b, int flags, void *stream) {
+    TMR_REQUIRE(prec_ok(prec) && ks_ok(ks));
+    TMR_REQUIRE(wpack && bias && headw && head_bias && box && b && U > 0 && H > 0 && W > 0 && N > 0);
+    TMR_REQUIRE(C0 >= 0 && C1 >= 0 && C0 + C1 > 0 && (C0 == 0 || xp0) && (C1 == 0 || xp1));
+    TMR_REQUIRE(prec == TMR_PREC_BF16 || (wmax && xmax));
+    TMR_REQUIRE(ntiles >= 0 && (ntiles == 0 || tiles));
+    TMR_REQUIRE(!(flags & (TMR_SPLIT_TILED_OUT | TMR_SPLIT_OUT_BF16 | TMR_SPLIT_XMAX_PER_PIXEL)));
+    TMR_REQUIRE(!acc_init || (flags & TMR_SPLIT_TILED_INIT));
+    TMR_REQUIRE(!(flags & TMR_SPLIT_INIT_BF16) || ((flags & TMR_SPLIT_TILED_INIT) && prec != TMR_PREC_F16X3));
+    TMR_REQUIRE((int64_t)H * W < (1ll << 29));
+    PArgs pa = {};
+    SArgs &a = pa.s;
+    a.x0 = static_cast<const char *>(xp0);
+    a.x1 = static_cast<const char *>(xp1);
+    a.unit_image = unit_image;
+    a.wp = static_cast<const char *>(wpack);
+    a.wmax = prec == TMR_PREC_BF16 ? nullptr : wmax;
+    a.xmax = prec == TMR_PREC_BF16 ? nullptr : xmax;
+    a.bias = bias;
+    a.headw = headw;
+    a.acc_init = acc_init;
+    a.NC0 = (int)tmr_cdiv(C0, CCH);
+    a.NC1 = (int)tmr_cdiv(C1, CCH);
+    a.U = U;
+    a.H = H;
+    a.W = W;
+    a.N = N;
+    a.NT = (int)tmr_cdiv(N, BM);
+    a.Npad = a.NT * BM;
+    a.TXN = (int)tmr_cdiv(W, TW);
+    a.MT = a.TXN * (int)tmr_cdiv(H, TH);
+    a.Hp = pad_h(H, ks);
+    a.Wp = pad_w(W, ks);
+    a.leaky = leaky;
+    a.flags = flags & 0xff;
+    a.EI = 1;
+    TMR_REQUIRE(tile_window(flags, a.NT, a.NT0, a.NTW));
+    if (ks != 3 || a.NTW > NWAVES) return TMR_E_UNSUPPORTED;
+    pa.head_bias = head_bias;
+    pa.box = box;
+    pa.tiles = tiles;
+    pa.b = b;
+    if (ntiles == 0) return TMR_OK;
+    hipStream_t s = tmr_stream(stream);
+    switch (prec) {
+        case TMR_PREC_F16X3: return launch_points<TMR_PREC_F16X3>(pa, ntiles, s);
+        case TMR_PREC_BF16: return launch_points<TMR_PREC_BF16>(pa, ntiles, s);
+        default: return launch_points<TMR_PREC_F16>(pa, ntiles, s);
+    }
 }

@@ -273,7 +273,9 @@ extern "C" int tmr_peaks_decode(const float *o, int input_is_prob, const float *
                                 float *box, float *ref, int32_t *counts, const void *exp_table,
                                 void *stream) {
     TMR_REQUIRE(o && params && prob && logits && box && ref && counts && U > 0 && H > 0 && W > 0);
-    TMR_REQUIRE((input_is_prob & ~(1 | TMR_PEAKS_PROB_SCRATCH)) == 0);
+    TMR_REQUIRE((input_is_prob & ~(1 | TMR_PEAKS_PROB_SCRATCH | TMR_PEAKS_FIND_ONLY | TMR_PEAKS_DECODE_ONLY)) == 0);
+    const bool find_only = input_is_prob & TMR_PEAKS_FIND_ONLY, decode_only = input_is_prob & TMR_PEAKS_DECODE_ONLY;
+    TMR_REQUIRE(!(find_only && decode_only));
     const int is_prob = input_is_prob & 1, scratch = (input_is_prob & TMR_PEAKS_PROB_SCRATCH) != 0;
     hipStream_t s = tmr_stream(stream);
     ExpTable et = {nullptr, nullptr};
@@ -281,6 +283,12 @@ extern "C" int tmr_peaks_decode(const float *o, int input_is_prob, const float *
         const char *base = reinterpret_cast<const char *>(exp_table);
         et.off = reinterpret_cast<const uint32_t *>(base + EXP_HEADER);
         et.lo = reinterpret_cast<const uint16_t *>(base + EXP_HEADER + 4 * 65537);
+    }
+    const int ny = (int)std::min<int64_t>(tmr_cdiv((int64_t)H * W, 256), 32);
+    if (decode_only) {  // the rows of an earlier TMR_PEAKS_FIND_ONLY call
+        hipLaunchKernelGGL(decode_kernel, dim3(U, ny), dim3(256), 0, s, reg, H, W, params, counts, ref, box, et);
+        TMR_CHECK_LAUNCH();
+        return TMR_OK;
     }
     TMR_REQUIRE(W <= PCHUNK / 2);  // (R + 2) W floats of LDS <= 3 * 8192 * 4 B
     const size_t lds = (size_t)(peak_rows(W) + 2) * W * sizeof(float);
@@ -295,12 +303,11 @@ extern "C" int tmr_peaks_decode(const float *o, int input_is_prob, const float *
         pm = prob;
     }
     // a few units: decode inside the finder (one launch less); many: chip-wide
-    const int fuse = U <= kFuseDecodeUnits;
+    const int fuse = U <= kFuseDecodeUnits && !find_only;
     hipLaunchKernelGGL(peaks_kernel, dim3(U), dim3(PNT), lds, s, pm, H, W, params, logits, box, ref, counts, reg,
                        fuse, et);
     TMR_CHECK_LAUNCH();
-    if (!fuse) {
-        const int ny = (int)std::min<int64_t>(tmr_cdiv((int64_t)H * W, 256), 32);
+    if (!fuse && !find_only) {
         hipLaunchKernelGGL(decode_kernel, dim3(U, ny), dim3(256), 0, s, reg, H, W, params, counts, ref, box, et);
         TMR_CHECK_LAUNCH();
     }

@@ -21,6 +21,11 @@ __global__ void heads_reduce_kernel(const float *__restrict__ part, int NT, int 
     float s[NHEAD];
 #pragma unroll
     for (int j = 0; j < NHEAD; ++j) s[j] = 0.0f;
+    if (!b) {  // objectness only: the regression heads' partials are not read
+        for (int t = 0; t < NT; ++t) s[4] += part[(((size_t)t * NHEAD + 4) * U + u) * HW + p];
+        o[i] = s[4] + hb[4];
+        return;
+    }
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int j = 0; j < NHEAD; ++j) s[j] += part[(((size_t)t * NHEAD + j) * U + u) * HW + p];

@@ -32,11 +32,11 @@ import numpy as np
 import torch
 
 from . import exp_table, host
-from ._lib import (PEAKS_PROB_SCRATCH, PREC_CODES, SPLIT_INIT_BCAST, SPLIT_INIT_BF16, SPLIT_OUT_BF16,
+from ._lib import (PEAKS_DECODE_ONLY, PEAKS_FIND_ONLY, PEAKS_PROB_SCRATCH, POINTS_TILE, PREC_CODES, SPLIT_INIT_BCAST, SPLIT_INIT_BF16, SPLIT_OUT_BF16,
                    SPLIT_TILED_INIT, SPLIT_TILED_OUT, SPLIT_UNITS_PER_IMAGE_SHIFT, SPLIT_XMAX_PER_PIXEL,
                    SPLIT_XMAX_PER_UNIT, SIZE_KINDS, XPACK_ONES, XPACK_UPSAMPLE,
                    UNIT_DTYPE, XCORR_ALGOS, TMRError, call, load, ptr,
-                   require_gpu, size, stream, xcorr)
+                   require_gpu, size, split_tile_window, stream, xcorr)
 
 NHEAD = 5
 NMS_SMALL = 256  # TMR_NMS_SMALL (include/tmr.h)
@@ -618,6 +618,13 @@ class TMREngine:
         self.last_decoder_flops = 0.0
         self.last_shared_flops = 0.0
         self.last_decoder_algo = None
+        # detect()'s regression route of the last call ("points" / "dense";
+        # None: the fused dense launch), its candidates and the points
+        # launch's direct conv FLOPs (whole tiles of POINTS_TILE points)
+        self.last_box_route = None
+        self.last_points = 0
+        self.last_points_flops = 0.0
+        self._box_ctx = None
         if cfg.decoder_kernel_size not in (1, 3, 5, 7):
             raise TMRError("decoder_kernel_size must be 1, 3, 5 or 7")
 
@@ -890,9 +897,12 @@ class TMREngine:
         return out, relu
 
     def decode(self, fp: torch.Tensor, f_tm: torch.Tensor, unit_image: Sequence[int],
-               feats: Optional[torch.Tensor] = None):
+               feats: Optional[torch.Tensor] = None, box_later: bool = False):
         """Decoders + heads over cat([fp[img(u)], f_TM[u]]) -> o [U,1,H,W], b [U,4,H,W]|None.
-        feats (the SAM features fp was projected from) enables the folded fp half."""
+        feats (the SAM features fp was projected from) enables the folded fp half.
+        box_later (box_at_peaks_ok() holds): only decoder_o's channel tiles
+        run; b comes back unwritten and box_at_points() / box_dense() fill it
+        from the launch's operands kept in self._box_ctx."""
         cfg = self.cfg
         U, C1, H, W = f_tm.shape
         dev = f_tm.device
@@ -989,16 +999,23 @@ class TMREngine:
             if acc0 is None and bplane is not None:  # unshared folded fp half: its bias plane
                 a0 = ptr(bplane)
                 fl = SPLIT_TILED_INIT | SPLIT_INIT_BCAST | (SPLIT_INIT_BF16 if self._plane16() else 0)
-            fl |= xpu | (self._units_per_image(unit_image, B) << SPLIT_UNITS_PER_IMAGE_SHIFT)
+            fl |= xpu
+            epi = self._units_per_image(unit_image, B) << SPLIT_UNITS_PER_IMAGE_SHIFT
+            # box_later: decoder_o's tiles only (the window's partials sit where
+            # the full launch writes them)
+            nbt = self._box_tiles() if box_later else 0
+            nt_all = (N + 127) // 128
+            win = split_tile_window(nbt, nt_all - nbt) if box_later else 0
             call("tmr_split_conv", ptr(xp0) if C0k else None, C0k, ptr(ui), ptr(xp1), C1,
                  U, H, W, ks, pc, ptr(wp[0]), ptr(wp[1]), ptr(xmax1), ptr(bias), N, 1, ptr(hw),
-                 a0, ptr(part), fl, stream())
+                 a0, ptr(part), fl | epi | win, stream())
             if ev is not None:
                 ev[1].record()
                 self.decoder_events.append(ev)
-            # direct conv FLOPs (the kernel executes 3 16-bit MFMA terms per
-            # product under the fp32 contract)
-            self.last_decoder_flops = 2.0 * H * W * N * (C0k + C1) * ks ** 2 * U
+            # direct conv FLOPs of the timed launch's channel tiles (the kernel
+            # executes 3 16-bit MFMA terms per product under the fp32 contract)
+            n_run = 128 * (nt_all - nbt) if box_later else N
+            self.last_decoder_flops = 2.0 * H * W * n_run * (C0k + C1) * ks ** 2 * U
             self.last_shared_flops = 2.0 * H * W * N * C0 * ks ** 2 * B if share else 0.0
             self.last_decoder_algo = "split"
             # o and b as contiguous views of ONE buffer (a graph replay then
@@ -1006,6 +1023,16 @@ class TMREngine:
             ob = torch.empty(U * (5 if cfg.box_reg else 1) * H * W, device=dev, dtype=torch.float32)
             o = ob[:U * H * W].view(U, 1, H, W)
             b = ob[U * H * W:].view(U, 4, H, W) if cfg.box_reg else None
+            if box_later:
+                call("tmr_heads_reduce", ptr(part[nbt * NHEAD * U * H * W:]), 128 * (nt_all - nbt), 128, U, H, W,
+                     ptr(hb), ptr(o), None, stream())
+                # everything the regression launches read (tensors kept alive here)
+                self._box_ctx = dict(
+                    args=(ptr(xp0) if C0k else None, C0k, ptr(ui), ptr(xp1), C1, U, H, W, ks, pc, ptr(wp[0]),
+                          ptr(wp[1]), ptr(xmax1), ptr(bias), N, 1, ptr(hw)),
+                    a0=a0, fl=fl, epi=epi, hb=hb, part=part, b=b, nbt=nbt, flops_per_point=2.0 * 128 * nbt *
+                    (C0k + C1) * ks ** 2, keep=(xp0, ui, xp1, wp, xmax1, bias, hw, acc0, bplane))
+                return o, b
             call("tmr_heads_reduce", ptr(part), N, 128, U, H, W, ptr(hb), ptr(o),
                  ptr(b) if b is not None else None, stream())
             return o, b
@@ -1024,6 +1051,85 @@ class TMREngine:
             lw, lb = self.P["ltrbs_head.head.0.weight"], self.P["ltrbs_head.head.0.bias"]
             b = self._conv("ltrbs", res["decoder_b"], lw, lb, False)
         return o, b
+
+    # ---- the regression map only where detect() reads it --------------------
+    # detect() returns kept boxes, and the decode reads b at the candidates
+    # alone (csrc/peaks.hip decode_one): a few percent of the pixels.  On its
+    # eager route (no speculative small NMS: more than GRAPH_MAX_UNITS units,
+    # or graphs off) detect() therefore runs decoder_o's tiles densely, finds
+    # the peaks, reads the counts back (the sync it always had) and computes
+    # decoder_b + ltrbs_head at the candidates (tmr_split_conv_points), bit
+    # for bit the dense values.  "auto" falls back to decoder_b's dense tiles
+    # when the candidates exceed BOX_POINTS_CROSSOVER of the pixels.
+    box_at_peaks = "auto"  # "auto" | "always" | "never"
+    # (dense decoder_b tiles' time per pixel) / (points launch's time per point), measured on one
+    # box at configs B-E (profiles/r07points/crossover.json): 3-term fp16 0.40-0.43, one term 0.29
+    BOX_POINTS_CROSSOVER = {"fp32": 0.40, "bf16": 0.28, "f16": 0.28}
+
+    def _box_tiles(self) -> int:
+        """decoder_b's 128-channel tiles at the front of decoder_b || decoder_o."""
+        return int(self.P["decoder_b.layer.0.weight"].shape[0]) // 128
+
+    def box_at_peaks_ok(self) -> bool:
+        """The points route's preconditions: one fused decoder layer with box
+        regression, kernel size 3 (other sizes stay on the dense launch),
+        decoder_b in 1..8 whole channel tiles, no per-image memo."""
+        cfg = self.cfg
+        if self.box_at_peaks == "never" or cfg.decoder_num_layer != 1 or not cfg.box_reg or \
+                cfg.decoder_kernel_size != 3 or self.reuse_image_work:
+            return False
+        if self.box_at_peaks not in ("auto", "always"):
+            raise TMRError("box_at_peaks must be 'auto', 'always' or 'never'")
+        nb = int(self.P["decoder_b.layer.0.weight"].shape[0])
+        return nb % 128 == 0 and 1 <= nb // 128 <= 8
+
+    def box_at_points(self, box: torch.Tensor, tiles: np.ndarray) -> None:
+        """b at the candidates of `tiles` (host.point_tiles), from the last
+        decode(box_later=True)'s operands."""
+        c = self._box_ctx
+        if len(tiles) == 0:
+            return
+        td = _h2d(np.ascontiguousarray(tiles, np.int32).reshape(-1), box.device)
+        call("tmr_split_conv_points", *c["args"], ptr(c["hb"]), c["a0"], ptr(box), ptr(td), len(tiles),
+             ptr(c["b"]), c["fl"] | split_tile_window(0, c["nbt"]), stream())
+
+    def box_dense(self) -> None:
+        """b everywhere: decoder_b's tiles of the dense heads launch."""
+        c = self._box_ctx
+        U, H, W = c["args"][5:8]
+        N = c["args"][14]
+        call("tmr_split_conv", *c["args"], c["a0"], ptr(c["part"]),
+             c["fl"] | c["epi"] | split_tile_window(0, c["nbt"]), stream())
+        scratch_o = torch.empty(U * H * W, device=c["b"].device, dtype=torch.float32)
+        call("tmr_heads_reduce", ptr(c["part"]), 128 * c["nbt"], 128, U, H, W, ptr(c["hb"]), ptr(scratch_o),
+             ptr(c["b"]), stream())
+
+    def _detect_box_at_peaks(self, feats, unit_image, boxes, params):
+        """detect()'s eager forward with the regression at the peaks:
+        objectness tiles, finder, counts read-back, points launch (or the
+        dense decoder_b tiles), decode.  Returns (logits, box, ref, counts,
+        counts_host)."""
+        r = self._forward_units_eager(feats, [int(i) for i in unit_image], boxes, box_later=True)
+        o, b = r["o"], r["b"]
+        U = o.shape[0]
+        H, W = o.shape[-2:]
+        logits, box, ref, counts, _ = self.peaks(o, None, params, want_prob=False, phase="find")
+        counts_host = counts.cpu().numpy()  # torch.where-style sync (TM_utils.py:254)
+        need = np.where(params["mode"] != 2, counts_host, 0)
+        self.last_points = int(need.sum())
+        dense = self.box_at_peaks == "auto" and \
+            self.last_points > self.BOX_POINTS_CROSSOVER[self.cfg.precision] * U * H * W
+        self.last_box_route = "dense" if dense else "points"
+        if dense:
+            self.box_dense()
+            self.last_points_flops = 0.0
+        else:
+            tiles = host.point_tiles(need, POINTS_TILE)
+            self.box_at_points(box, tiles)
+            self.last_points_flops = self._box_ctx["flops_per_point"] * POINTS_TILE * len(tiles)
+        self._box_ctx = None
+        self.peaks(o, b, params, want_prob=False, phase="decode", found=(logits, box, ref, counts))
+        return logits, box, ref, counts, counts_host
 
     @staticmethod
     def _units_per_image(unit_image, B: int) -> int:
@@ -1150,7 +1256,7 @@ class TMREngine:
         return self._forward_units_eager(feats, unit_image, unit_boxes, want_aux)
 
     def _forward_units_eager(self, feats: torch.Tensor, unit_image: Sequence[int], unit_boxes,
-                             want_aux: bool = False):
+                             want_aux: bool = False, box_later: bool = False):
         m = self._fp_memo
         # the projection memo follows the input_proj parameters' storage,
         # version AND identity (as _PackCache), and the path options that
@@ -1182,7 +1288,7 @@ class TMREngine:
             split1 = self.cfg.decoder_num_layer == 1
             f_tm, relu = self.match(fp, unit_image, np.asarray(unit_boxes, np.float32), want_aux,
                                     allow_bf16=split1 and not want_aux)
-        o, b = self.decode(fp, f_tm, unit_image, feats)
+        o, b = self.decode(fp, f_tm, unit_image, feats, box_later=box_later)
         return dict(o=o, b=b, f_tm_relu=relu, f0=f0, fp=fp)
 
     # ------------------------------------------------------------ post
@@ -1193,10 +1299,14 @@ class TMREngine:
 
     @staticmethod
     def peaks(o: torch.Tensor, b: Optional[torch.Tensor], params: np.ndarray,
-              input_is_prob: bool = False, want_prob: bool = True):
+              input_is_prob: bool = False, want_prob: bool = True, phase: Optional[str] = None,
+              found=None):
         """Peak finder + decode per unit -> (logits, box, ref, counts, prob)
         with per-unit stride H*W; prob is None unless want_prob (without it
-        the kernel skips the sigmoid of pixels that cannot matter)."""
+        the kernel skips the sigmoid of pixels that cannot matter).
+        phase "find": the finder alone (b unused; each box row holds its
+        candidate's pixel index); phase "decode": the decode alone over
+        found = the (logits, box, ref, counts) of a "find" call."""
         require_gpu(o, "objectness")
         o = o.float().contiguous()
         U = o.shape[0]
@@ -1204,14 +1314,22 @@ class TMREngine:
         dev = o.device
         cap = H * W
         prm = _h2d(params.view(np.uint8), dev, tag="peak_params")
+        bb = b.float().contiguous() if b is not None else None
+        tab = exp_table.device_table(dev) if TMREngine.exp_mode == "reference" else None
+        flags = int(input_is_prob) | (0 if want_prob else PEAKS_PROB_SCRATCH)
+        if phase == "decode":
+            logits, box, ref, counts = found
+            call("tmr_peaks_decode", ptr(o), flags | PEAKS_DECODE_ONLY, ptr(bb) if bb is not None else None,
+                 U, H, W, ptr(prm), ptr(o), ptr(logits), ptr(box), ptr(ref), ptr(counts),
+                 ptr(tab) if tab is not None else None, stream())
+            return logits, box, ref, counts, None
         prob = torch.empty((U, H, W), device=dev, dtype=torch.float32)  # (scratch unless want_prob)
         logits = torch.empty((U * cap, 2), device=dev, dtype=torch.float32)
         box = torch.empty((U * cap, 4), device=dev, dtype=torch.float32)
         ref = torch.empty((U * cap, 2), device=dev, dtype=torch.float32)
         counts = torch.empty(U, device=dev, dtype=torch.int32)
-        bb = b.float().contiguous() if b is not None else None
-        tab = exp_table.device_table(dev) if TMREngine.exp_mode == "reference" else None
-        flags = int(input_is_prob) | (0 if want_prob else PEAKS_PROB_SCRATCH)
+        if phase == "find":
+            flags |= PEAKS_FIND_ONLY
         call("tmr_peaks_decode", ptr(o), flags, ptr(bb) if bb is not None else None,
              U, H, W, ptr(prm), ptr(prob), ptr(logits), ptr(box), ptr(ref), ptr(counts),
              ptr(tab) if tab is not None else None, stream())
@@ -1410,7 +1528,13 @@ class TMREngine:
             out = g.replay(feats.float().contiguous(), host_in)
             for k, v in g.last.items():
                 setattr(self, k, v)
+        elif spec is None and self.box_at_peaks_ok():
+            # the unspeculated eager route: the regression only at the peaks
+            logits, box, ref, counts, counts_host = self._detect_box_at_peaks(feats, unit_image, boxes, params)
+            self.last_nms_small = False
+            return self.nms(logits, box, ref, counts, counts_host, unit_off, seg, iou_threshold)
         else:
+            self.last_box_route = None
             out = self._forward_peaks(feats, unit_image, boxes, params, spec)
         logits, box, ref, counts = out[:4]
         if spec is not None:

@@ -256,3 +256,24 @@ def nms_offsets(counts: np.ndarray, seg_units: np.ndarray):
     nb_off = np.zeros(G + 1, np.int64)
     nb_off[1:] = np.cumsum((n + 63) // 64)
     return cand_off, nb_off, int(n.max()) if G else 0
+
+
+def point_tiles(counts: np.ndarray, tile: int) -> np.ndarray:
+    """The tile list of tmr_split_conv_points: int32 [n, 3] rows (unit, first
+    candidate, count) covering counts[u] candidates of every unit in tiles of
+    at most `tile`, unit after unit; a tile never spans units and a unit
+    with counts[u] == 0 (no candidate, or no regression: the caller zeroes
+    mode-2 units) gets none."""
+    counts = np.asarray(counts, np.int64)
+    nt = (counts + tile - 1) // tile
+    total = int(nt.sum())
+    out = np.zeros((total, 3), np.int32)
+    if total == 0:
+        return out
+    unit = np.repeat(np.arange(len(counts)), nt)
+    start = np.cumsum(nt) - nt
+    first = (np.arange(total) - start[unit]) * tile
+    out[:, 0] = unit
+    out[:, 1] = first
+    out[:, 2] = np.minimum(counts[unit] - first, tile)
+    return out
