@@ -82,7 +82,8 @@ const char *tmr_strerror(int rc);
  *   TMR_SIZE_WPACK          (N, C0, C1, ks, prec)       bytes, tmr_split_wpack
  *   TMR_SIZE_ACC            (U, N, H, W)                floats, TMR_SPLIT_TILED_OUT slabs
  *   TMR_SIZE_NMS_WORK       (total_cand, sum_nb, max_cand, G)  bytes, tmr_nms
- *   TMR_SIZE_STATS_WORK     (B)                         bytes, tmr_feature_stats */
+ *   TMR_SIZE_STATS_WORK     (B)                         bytes, tmr_feature_stats
+ *   TMR_SIZE_GT_WORK        (G_total, NI, H, W, U)      bytes, tmr_gt_loss */
 enum {
     TMR_SIZE_TEMPLATE_SPLIT = 1,
     TMR_SIZE_HEADS_PARTIALS = 2,
@@ -90,7 +91,8 @@ enum {
     TMR_SIZE_WPACK = 4,
     TMR_SIZE_ACC = 5,
     TMR_SIZE_NMS_WORK = 6,
-    TMR_SIZE_STATS_WORK = 7
+    TMR_SIZE_STATS_WORK = 7,
+    TMR_SIZE_GT_WORK = 8
 };
 int64_t tmr_size(int kind, int64_t d0, int64_t d1, int64_t d2, int64_t d3, int64_t d4, int64_t d5);
 
@@ -368,6 +370,112 @@ int tmr_maxpool3x3(const float *x, int64_t planes, int H, int W, int mask9, floa
 int tmr_peaks_decode(const float *o, int input_is_prob, const float *reg, int U, int H, int W,
                      const tmr_peak_param_t *params, float *prob, float *logits, float *box,
                      float *ref, int32_t *counts, const void *exp_table, void *stream);
+
+/* ---- (§8 GT_map + SetCriterion_TM) evaluation losses ------------------------
+ * What the reference's trainer.py:75-153 computes on every validation / test
+ * step when ground truth is present: GT_map.Get_pred_gts (utils/TM_utils.py:
+ * 94-222) and SetCriterion_TM (criterion/criterions_TM.py) for ONE level of
+ * U (image, exemplar) units over NI images with their GT boxes.  No gradient
+ * is produced: training and backward are out of scope.
+ *
+ * Per GT box g = (x1,y1,x2,y2) of an image (fp32, every op separately rounded,
+ * divisions correctly rounded): cx = (x2+x1)/2, cy = (y2+y1)/2, ws = x2-x1,
+ * hs = y2-y1, ratio = -hs/ws (inf / NaN for ws = 0: both tests below are then
+ * false by IEEE comparison, as in the reference), bias_p = fl32((1-pt)/(1+pt))
+ * * hs and bias_n likewise from nt (the quotient in double on the host, rounded
+ * once), area = (x2-x1)*(y2-y1).
+ * Per pixel i = y*W + x: cxs = fl32(x)/fl32(W), cys = fl32(y)/fl32(H),
+ * rx = |cxs-cx|, ry = |cys-cy|, inpos = (ratio*rx + bias_p) >= ry, inneg =
+ * (ratio*rx + bias_n) < ry (mul and add not fused).  center_g = the lowest-index
+ * pixel minimising fl32(rx+ry).  pt == 1.0: inpos := is_center; nt == 1.0:
+ * inneg := !is_center.  pos_g = inpos | is_center on the last level, inpos
+ * otherwise.  Per image and pixel: any_pos, all_pos, any_notneg = any_g(!inneg),
+ * and target = the first g minimising (pos_g ? area : 1e8f) (0 when no pos_g).
+ * Per unit: nib = pad_y <= y < H-pad_y && pad_x <= x < W-pad_x (the exemplar's
+ * boundary rectangle, TM_utils.py:36-54); positive = nib & any_pos; ignore =
+ * nib & !all_pos & any_notneg; negative = !(positive | ignore); gt_map = 1.0
+ * positive, 0.5 ignore only, 0.0 negative.  So the box loop runs once per
+ * IMAGE; a unit only applies its rectangle.
+ * Prediction row of a positive pixel (TM_utils.py:183-193): xy = (cxs,cys) +
+ * reg[0:2] * (sw,sh) ((1,1) for mode 1), wh = exp(reg[2:4]) * (scale_w,
+ * scale_h), zero regressions for mode 2, the exp as tmr_peaks_decode's
+ * (exp_table); its GT row is (cx, cy, ws, hs) of box target.  A unit with no
+ * positive pixel contributes the row [0,0,1e-14,1e-14] as both.
+ * Element losses (fp64 evaluation of the fp32 samples / rows): ce = BCE with
+ * logits (positives: target 1, negatives: target 0, ignore pixels excluded),
+ * with focal: at * (1-exp(-ce))^2 * ce, at = 0.25 positives / 0.75 negatives;
+ * giou = torchvision generalized_box_iou_loss(eps = 1e-13) on the cxcywh ->
+ * xyxy rows: intersection only where both extents are > 0, iou = I/(U+eps),
+ * 1 - iou + (Ac-U)/(Ac+eps).  Sums are fp64 in a fixed order (a unit's pixels
+ * in TMR_GT_SLICES slices, then the slices in order): a repeat run, or the
+ * unit inside another batch, gives the same bits.
+ *
+ * phase (a bit set; the steps run in this order):
+ *  TMR_GT_ASSIGN  box records, per-image classes, then per unit gt_map
+ *                 [U,1,H,W], target [U,H,W] (int32, box index local to the
+ *                 image; 0 where not positive) and counts [U][2] = positive,
+ *                 negative pixels.  With TMR_GT_LOSS in the same call, also
+ *                 sums [U][2] (fp64) = {sum ce, sum giou} straight from o /
+ *                 reg, no gather; a unit with no positive pixel has sum giou =
+ *                 the dummy pair's loss and counts 1 row towards num_positive
+ *                 (the caller's max(counts[u][0], 1)).
+ *  TMR_GT_LOSS    only together with TMR_GT_ASSIGN (above).
+ *  TMR_GT_GATHER  from gt_map / target / counts of an earlier ASSIGN (same
+ *                 arguments): unit u's samples at obj_out + samp_off[u]:
+ *                 o at its positive pixels (row-major), then at its negative
+ *                 pixels; label_out the same layout of 1 / 0; rows_pred /
+ *                 rows_gt [.,4] at row row_off[u]: one per positive pixel, or
+ *                 the dummy row.  samp_off / row_off (device int64[U]) are the
+ *                 host's prefix sums of counts (one read-back, as the
+ *                 reference's boolean indexing syncs).
+ *  TMR_GT_ROWS    alone: the same element losses over gathered lists:
+ *                 obj_out / label_out [n_samples], rows_pred / rows_gt
+ *                 [n_rows,4] -> sums[0..1] = {sum ce, sum giou}.
+ * ASSIGN / GATHER need boxes (device float[G_total][4], finite), box_off
+ * (device int32[NI+1], image m's boxes box_off[m] .. box_off[m+1]-1), units
+ * (device tmr_gt_unit_t[U]) and min_boxes = the smallest per-image box count
+ * as the host counted it: 0 (an image without GT, where the reference's
+ * torch.min raises) is refused.  Each image needs fewer than 2^29 boxes and
+ * H*W must fit int32.  work: TMR_SIZE_GT_WORK(G_total, NI, H, W, U) bytes
+ * (TMR_GT_ROWS: any G_total, NI, H, W, U >= 1). */
+typedef struct tmr_gt_unit {
+    int32_t image;           /* index into box_off: the image whose boxes apply     */
+    int32_t pad_x, pad_y;    /* boundary pads (TM_utils.py:36-48), >= 0             */
+    int32_t mode;            /* as tmr_peak_param_t.mode                            */
+    float scale_w, scale_h;  /* clamped exemplar w,h or 1 (TM_utils.py:128-135)     */
+    int32_t pad_[2];
+} tmr_gt_unit_t;
+#define TMR_GT_ASSIGN 1
+#define TMR_GT_LOSS 2
+#define TMR_GT_GATHER 4
+#define TMR_GT_ROWS 8
+#define TMR_GT_SLICES 16
+typedef struct tmr_gt_loss_args {
+    const float *o;            /* [U,1,H,W] objectness logits (LOSS, GATHER)          */
+    const float *reg;          /* [U,4,H,W] regressions; NULL only if every mode is 2 */
+    const float *boxes;
+    const int32_t *box_off;
+    const tmr_gt_unit_t *units;
+    const void *exp_table;     /* nullable, as tmr_peaks_decode                       */
+    void *work;
+    float *gt_map;
+    int32_t *target;
+    int32_t *counts;
+    double *sums;
+    const int64_t *samp_off;
+    const int64_t *row_off;
+    float *obj_out;
+    float *label_out;
+    float *rows_pred;
+    float *rows_gt;
+    double positive_threshold, negative_threshold;
+    int64_t n_samples, n_rows; /* TMR_GT_ROWS                                         */
+    int32_t U, NI, H, W;
+    int32_t G_total, min_boxes;
+    int32_t last_level, focal;
+    int32_t phase, pad_;
+} tmr_gt_loss_args_t;
+int tmr_gt_loss(const tmr_gt_loss_args_t *args, void *stream);
 
 /* ---- (a17-a19) per-image greedy NMS over the exemplar-ordered union --------
  * torchvision.ops.nms (utils/TM_utils.py:317-323) on, per image g, the

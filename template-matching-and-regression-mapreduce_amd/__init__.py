@@ -12,7 +12,8 @@ from .engine import PathConfig, TMREngine, conv2d_split  # noqa: F401
 from .matching_net import Backbone_Encoder, build_encoder, build_model, matching_net  # noqa: F401
 from .regression_head import BboxesHead, Decoder_model, ObjectnessHead  # noqa: F401
 from .template_matching import TemplateMatching  # noqa: F401
-from .tm_utils import (NMS, Get_pred_boxes, Make_Template_size_predictions,  # noqa: F401
+from .criterion import SetCriterion_TM, WeightedFocalLoss, build_criterion, gIoU_loss  # noqa: F401
+from .tm_utils import (NMS, GT_map, Get_pred_boxes, Make_Template_size_predictions,  # noqa: F401
                        NMS_process, adaptive_kernel_generater, calc_area, custom_shape_3x3_maxpool2d,
                        map_normalization)
 
@@ -21,5 +22,6 @@ __all__ = [
     "build_model", "Backbone_Encoder", "build_encoder", "Get_pred_boxes", "NMS", "NMS_process",
     "adaptive_kernel_generater", "Make_Template_size_predictions", "custom_shape_3x3_maxpool2d",
     "calc_area", "map_normalization", "TMREngine", "PathConfig",
+    "GT_map", "SetCriterion_TM", "build_criterion", "gIoU_loss", "WeightedFocalLoss",
     "TMRError", "build_backbone", "register_backbone", "unregister_backbone", "FeatureInput",
 ]

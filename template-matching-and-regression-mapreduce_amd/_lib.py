@@ -37,6 +37,13 @@ PEAK_DTYPE = np.dtype({
     "itemsize": 24,
 })
 
+GT_UNIT_DTYPE = np.dtype({  # tmr_gt_unit_t
+    "names": ["image", "pad_x", "pad_y", "mode", "scale_w", "scale_h", "pad_"],
+    "formats": [np.int32, np.int32, np.int32, np.int32, np.float32, np.float32, (np.int32, 2)],
+    "offsets": [0, 4, 8, 12, 16, 20, 24],
+    "itemsize": 32,
+})
+
 TEMPLATE_ROI_ALIGN = 0
 TEMPLATE_PROTOTYPE = 1
 
@@ -57,7 +64,10 @@ XCORR_ALGOS = {"auto": 0, "valu": 1, "mfma": 2}
 XPACK_UPSAMPLE, XPACK_ONES = 1, 2  # tmr_split_xpack `up` bits
 # tmr_size kinds
 SIZE_KINDS = {"template_split": 1, "heads_partials": 2, "xpack": 3, "wpack": 4, "acc": 5, "nms_work": 6,
-              "stats_work": 7}
+              "stats_work": 7, "gt_work": 8}
+# tmr_gt_loss_args_t.phase bits; TMR_GT_SLICES
+GT_ASSIGN, GT_LOSS, GT_GATHER, GT_ROWS = 1, 2, 4, 8
+GT_SLICES = 16
 ABI_VERSION = 3
 
 _P = ctypes.c_void_p
@@ -74,6 +84,18 @@ class XcorrArgs(ctypes.Structure):
                 ("U", ctypes.c_int32), ("max_ht", ctypes.c_int32), ("max_wt", ctypes.c_int32),
                 ("squeeze", ctypes.c_int32), ("algo", ctypes.c_int32), ("min_k", ctypes.c_int32),
                 ("prec", ctypes.c_int32), ("out_bf16", ctypes.c_int32)]
+
+
+class GtLossArgs(ctypes.Structure):
+    """tmr_gt_loss_args_t (include/tmr.h)."""
+    _fields_ = [("o", _P), ("reg", _P), ("boxes", _P), ("box_off", _P), ("units", _P), ("exp_table", _P),
+                ("work", _P), ("gt_map", _P), ("target", _P), ("counts", _P), ("sums", _P), ("samp_off", _P),
+                ("row_off", _P), ("obj_out", _P), ("label_out", _P), ("rows_pred", _P), ("rows_gt", _P),
+                ("positive_threshold", _D), ("negative_threshold", _D), ("n_samples", _L), ("n_rows", _L),
+                ("U", ctypes.c_int32), ("NI", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("G_total", ctypes.c_int32), ("min_boxes", ctypes.c_int32), ("last_level", ctypes.c_int32),
+                ("focal", ctypes.c_int32), ("phase", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -101,6 +123,7 @@ SIGNATURES = {
     "tmr_nms": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _D, _P, _P, _P, _P, _P, _P, _P]),
     "tmr_nms_small": (_I, [_P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P, _P, _P]),
     "tmr_feature_stats": (_I, [_P, _I, _L, _P, _P, _P]),
+    "tmr_gt_loss": (_I, [ctypes.POINTER(GtLossArgs), _P]),
     "tmr_exp_table_encode": (_L, [_P, _L, _P, _L]),
     "tmr_exp_table_decode": (_L, [_P, _L, _P, _L]),
 }
@@ -192,6 +215,28 @@ def xcorr(**fields) -> None:
 
 
 _XPTR = {"f", "templates", "units", "img_units", "scale", "out", "relu_out", "work", "out_absmax", "tmpl_split"}
+
+
+_GT_FIELDS = {n for n, _ in GtLossArgs._fields_} - {"pad_"}
+
+
+def gt_loss_args(**fields) -> GtLossArgs:
+    """A tmr_gt_loss_args_t from keyword fields (pointer fields take ptr(...)
+    values or None; omitted fields are 0 / NULL).  A name the struct does not
+    have is an error, never silently dropped."""
+    unknown = set(fields) - _GT_FIELDS
+    if unknown:
+        raise TMRError(f"tmr_gt_loss_args_t has no field(s) {sorted(unknown)}")
+    a = GtLossArgs()
+    for k, v in fields.items():
+        if v is not None:
+            setattr(a, k, v)
+    return a
+
+
+def gt_loss(stream_=None, **fields) -> None:
+    """tmr_gt_loss(&args, stream)."""
+    check(load().tmr_gt_loss(ctypes.byref(gt_loss_args(**fields)), stream_), "tmr_gt_loss")
 
 
 def require_gpu(t: torch.Tensor, name: str = "input") -> None:

@@ -13,6 +13,7 @@ TMR_INTERNAL int64_t tmr_wpack_bytes(int N, int C0, int C1, int ks, int prec);
 TMR_INTERNAL int64_t tmr_acc_floats(int U, int N, int H, int W);
 TMR_INTERNAL int64_t tmr_nms_work_bytes(int64_t total_cand, int64_t sum_nb, int64_t max_cand, int G);
 TMR_INTERNAL int64_t tmr_stats_work_bytes(int B);
+TMR_INTERNAL int64_t tmr_gt_work_bytes(int64_t G, int64_t NI, int64_t H, int64_t W, int64_t U);
 
 extern "C" int tmr_version(void) { return TMR_ABI_VERSION; }
 
@@ -40,6 +41,7 @@ extern "C" int64_t tmr_size(int kind, int64_t d0, int64_t d1, int64_t d2, int64_
         case TMR_SIZE_ACC: return small ? tmr_acc_floats((int)d0, (int)d1, (int)d2, (int)d3) : -1;
         case TMR_SIZE_NMS_WORK: return fits_int(d3) ? tmr_nms_work_bytes(d0, d1, d2, (int)d3) : -1;
         case TMR_SIZE_STATS_WORK: return fits_int(d0) ? tmr_stats_work_bytes((int)d0) : -1;
+        case TMR_SIZE_GT_WORK: return tmr_gt_work_bytes(d0, d1, d2, d3, d4);
         default: return -1;
     }
 }

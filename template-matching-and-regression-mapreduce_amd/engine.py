@@ -1336,6 +1336,45 @@ class TMREngine:
         return logits, box, ref, counts, (prob if want_prob else None)
 
     @staticmethod
+    def eval_loss(o, b, unit_image: Sequence[int], unit_boxes, gt_boxes, *, positive_threshold: float,
+                  negative_threshold: float, focal: bool = False, ablation_no_box_regression: bool = False,
+                  regression_scaling_imgsize: bool = False, regression_scaling_WH_only: bool = False,
+                  groups: Optional[Sequence[int]] = None):
+        """The evaluation losses of trainer.py:75-153 (GT_map.Get_pred_gts +
+        SetCriterion_TM) fused on the GPU (tmr_gt_loss): no [H*W, G] matrix,
+        no gather and no sync.  o / b: the objectness [U,1,H,W] and regression
+        [U,4,H,W] maps of forward_units, or lists of them over levels (b may
+        be None with ablation_no_box_regression); unit_image[u] indexes
+        gt_boxes (a list of per-image [G,4] xyxy boxes, host arrays preferred);
+        unit_boxes [U,4] are the exemplars.  `groups` [U] names the units that
+        share one num_positive -- one group per model() call of the trainer:
+        the whole batch in each_step (None), one exemplar in
+        each_step_multi_exemplars.  Returns loss_ce / loss_giou (fp32, 0-d, or
+        [groups] when groups is given; the mean over levels), gt_map (per
+        level [U,1,H,W]) and the last level's per-unit sums [U,2] fp64
+        {sum ce, sum giou}, counts [U,2] int32 {positive, negative pixels} and
+        target [U,H,W].  Outputs carry no autograd graph: training and
+        backward are out of scope."""
+        from . import gt_loss as gl
+
+        os_ = list(o) if isinstance(o, (list, tuple)) else [o]
+        bs_ = list(b) if isinstance(b, (list, tuple)) else [b] * len(os_)
+        boxes = np.asarray(unit_boxes, np.float32).reshape(-1, 4)
+        gtb = gl.host_boxes(gt_boxes)
+        ces, gis, maps = [], [], []
+        for lv, (ol, bl) in enumerate(zip(os_, bs_)):
+            H, W = ol.shape[-2:]
+            units = host.gt_units(boxes, unit_image, H, W, not ablation_no_box_regression,
+                                  regression_scaling_imgsize, regression_scaling_WH_only)
+            st = gl.assign(ol, None if ablation_no_box_regression else bl, units, gtb, positive_threshold,
+                           negative_threshold, lv == len(os_) - 1, focal, with_loss=True)
+            ce, gi = gl.group_losses(st.sums, st.counts, groups)
+            ces.append(ce); gis.append(gi); maps.append(st.gt_map)
+        return dict(loss_ce=torch.stack(ces).mean(0), loss_giou=torch.stack(gis).mean(0),
+                    gt_map=maps if isinstance(o, (list, tuple)) else maps[0],
+                    sums=st.sums, counts=st.counts, target=st.target)
+
+    @staticmethod
     def nms(logits, box, ref, counts: torch.Tensor, counts_host: np.ndarray,
             unit_off: torch.Tensor, seg_units: np.ndarray, iou_threshold: float,
             want_keep: bool = False):

@@ -12,7 +12,7 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PEAK_DTYPE, TEMPLATE_PROTOTYPE, TEMPLATE_ROI_ALIGN, UNIT_DTYPE
+from ._lib import GT_UNIT_DTYPE, PEAK_DTYPE, TEMPLATE_PROTOTYPE, TEMPLATE_ROI_ALIGN, UNIT_DTYPE
 
 f32 = np.float32
 
@@ -239,6 +239,58 @@ def peak_params(boxes: np.ndarray, H: int, W: int, cls_ths: float, box_reg: bool
     P["mask"] = mask
     P["mode"] = mode
     return P
+
+
+def boundary_pads(boxes: np.ndarray, H: int, W: int):
+    """(pad_x, pad_y) int arrays of GT_map.Get_not_in_boundary (TM_utils.py:36-48):
+    the clamped exemplar snapped outwards to pixels, made odd, halved -- the
+    same fp32 products as template_size."""
+    c = clamp01_vec(np.asarray(boxes, np.float32).reshape(-1, 4))
+    x1 = np.floor((c[:, 0] * f32(W)).astype(np.float32)).astype(np.int64)
+    x2 = np.ceil((c[:, 2] * f32(W)).astype(np.float32)).astype(np.int64)
+    y1 = np.floor((c[:, 1] * f32(H)).astype(np.float32)).astype(np.int64)
+    y2 = np.ceil((c[:, 3] * f32(H)).astype(np.float32)).astype(np.int64)
+    x2 -= ((x2 - x1) % 2 == 0)
+    y2 -= ((y2 - y1) % 2 == 0)
+    return (x2 - x1) // 2, (y2 - y1) // 2
+
+
+def gt_units(boxes: np.ndarray, unit_image: Sequence[int], H: int, W: int, box_reg: bool = True,
+             ablation_b: bool = False, ablation_c: bool = False) -> np.ndarray:
+    """tmr_gt_unit_t per (image, exemplar) unit for tmr_gt_loss: the boundary
+    pads (TM_utils.py:36-48), the decode scales and mode of peak_params
+    (TM_utils.py:128-135, 183-187) and the image whose GT boxes apply.  An
+    exemplar that snaps to an empty pixel range (a negative pad, where the
+    reference's slice wraps around) is refused."""
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    U = boxes.shape[0]
+    img = np.asarray(unit_image, np.int64).reshape(-1)
+    if img.shape[0] != U:
+        raise ValueError("one image index per unit")
+    pad_x, pad_y = boundary_pads(boxes, H, W)
+    if U and (pad_x.min() < 0 or pad_y.min() < 0):
+        raise ValueError("an exemplar box selects an empty pixel range")
+    pp = peak_params(boxes, H, W, 0.0, box_reg, ablation_b, ablation_c)
+    G = np.zeros(U, GT_UNIT_DTYPE)
+    G["image"] = img
+    G["pad_x"], G["pad_y"] = pad_x, pad_y
+    G["mode"] = pp["mode"]
+    G["scale_w"], G["scale_h"] = pp["scale_w"], pp["scale_h"]
+    return G
+
+
+def gt_box_table(gt_boxes):
+    """(boxes [G_total,4] fp32, box_off [NI+1] int32, min_boxes) of a list of
+    per-image [G,4] box arrays; the boxes must be finite."""
+    arrs = [np.asarray(b, np.float32).reshape(-1, 4) for b in gt_boxes]
+    if not arrs:
+        raise ValueError("no images")
+    cat = np.concatenate(arrs) if arrs else np.zeros((0, 4), np.float32)
+    if not np.isfinite(cat).all():
+        raise ValueError("GT boxes must be finite")
+    off = np.zeros(len(arrs) + 1, np.int32)
+    off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    return np.ascontiguousarray(cat), off, int(min(a.shape[0] for a in arrs))
 
 
 def nms_offsets(counts: np.ndarray, seg_units: np.ndarray):

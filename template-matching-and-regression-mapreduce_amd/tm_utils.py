@@ -79,6 +79,53 @@ def _dummy(dtype, device):
     return tuple(t.clone() for t in d)
 
 
+class GT_map:
+    """TM_utils.py:20-222, the evaluation form: ``Get_pred_gts`` builds the
+    target maps and the sample / row lists on the GPU (tmr_gt_loss) without
+    the reference's [H*W, G] matrices.  Only the constructor and
+    ``Get_pred_gts`` are provided.  Outputs carry no autograd graph: training
+    and backward are out of scope."""
+
+    def __init__(self, args):
+        self.positive_threshold = args.positive_threshold
+        self.negative_threshold = args.negative_threshold
+        self.box_reg = not args.ablation_no_box_regression
+
+    def Get_pred_gts(self, pred_objectness, pred_regressions, gt_boxes, exemplars, batch):
+        """TM_utils.py:94-222.  pred_objectness / pred_regressions: lists over
+        levels of [B,1,H,W] / [B,4,H,W]; gt_boxes: B per-image [G,4] boxes;
+        exemplars[b][0]: image b's exemplar.  Returns (preds, gts, gt_maps)
+        with the reference's keys, dtypes and row order; one count read-back
+        per level, as the reference's boolean indexing syncs."""
+        from . import gt_loss as gl
+
+        require_gpu(pred_objectness[0], "pred_objectness")
+        B = len(gt_boxes)
+        boxes = np.stack([_box_host(exemplars[b][0]) for b in range(B)])
+        gtb = gl.host_boxes(gt_boxes)
+        ab_b = bool(batch["regression_ablation_b"])
+        ab_c = bool(batch["regression_ablation_c"])
+        preds = {"objectness": [], "regressions": []}
+        gts = {"objectness": [], "regressions": [], "weight_objectness": [], "weight_regressions": []}
+        gt_maps = []
+        nl = len(pred_objectness)
+        for lv, (o, reg) in enumerate(zip(pred_objectness, pred_regressions)):
+            H, W = o.shape[-2:]
+            units = host.gt_units(boxes, np.arange(B), H, W, self.box_reg, ab_b, ab_c)
+            st = gl.assign(o[:B], reg[:B] if self.box_reg else None, units, gtb, self.positive_threshold,
+                           self.negative_threshold, lv == nl - 1)
+            obj, lab, rp, rg, _ = gl.gather(st)
+            dt = o.dtype
+            preds["objectness"].append(obj if dt == torch.float32 else obj.to(dt))
+            preds["regressions"].append(rp if dt == torch.float32 else rp.to(dt))
+            gts["objectness"].append(lab if dt == torch.float32 else lab.to(dt))
+            gts["regressions"].append(rg)
+            gts["weight_objectness"].append(None)
+            gts["weight_regressions"].append(None)
+            gt_maps.append(st.gt_map)
+        return preds, gts, gt_maps
+
+
 def Get_pred_boxes(pred_objectness, pred_regressions, exemplars, batch, cls_ths=0.1, box_reg=True,
                    input_is_prob=False):
     """TM_utils.py:224-305.  pred_objectness: list over levels of [B,1,H,W]
