@@ -53,9 +53,9 @@ typedef struct tmr_unit {
     float roi[4];          /* roi_align box in feature px (x1,y1,x2,y2), :61-63   */
     int32_t pbox[4];       /* prototype snapped box (x1,y1,x2,y2), :49-50         */
     int64_t tmpl_offset;   /* float offset of this unit's [C,ht,wt] template      */
-    int32_t row_offset;    /* sum of ht * tsplit_nk(wt) over the units before this */
-                           /* one (the MFMA correlation's split-template rows,    */
-                           /* tmr_template_split)                                  */
+    int32_t row_offset;    /* sum of na(ht) * nb(wt) over the units before this    */
+                           /* one: the MFMA correlation's template windows per    */
+                           /* channel (tmr_template_split defines na, nb)         */
     int32_t pad_;
 } tmr_unit_t;
 
@@ -75,7 +75,10 @@ const char *tmr_strerror(int rc);
  * tmr_size(kind, d0..d5) returns the size of a buffer the caller allocates
  * (bytes, or floats where noted), or -1 for invalid dimensions; unused
  * dimensions are 0.
- *   TMR_SIZE_TEMPLATE_SPLIT (U, C, total_rows)          bytes, tmr_template_split
+ *   TMR_SIZE_TEMPLATE_SPLIT (U, C, total_rows)          bytes, tmr_template_split: C *
+ *                                                       total_rows * 2 fragments of 1024 B,
+ *                                                       then 4 * U * C bytes of exponents
+ *                                                       (total_rows = sum of na * nb windows)
  *   TMR_SIZE_HEADS_PARTIALS (N, U, H, W)                floats, tmr_split_conv heads
  *   TMR_SIZE_XPACK          (S, C, H, W, ks, prec)      bytes, tmr_split_xpack (H, W at
  *                                                       the output resolution)
@@ -161,19 +164,38 @@ typedef struct tmr_xcorr_args {
 } tmr_xcorr_args_t;
 int tmr_xcorr(const tmr_xcorr_args_t *args, void *stream);
 /* Operand prep of the MFMA correlation: per (unit u, channel c) template
- * T = templates[units[u].tmpl_offset + c*ht*wt ...], t * 2^-e = th + tl with
- * fp16 hi/lo parts and 2^-e the power-of-two scale of max |T| (max |t| 2^-e <
- * 2^14), written as the kernel's MFMA A fragments: with nk(wt) = 1 if
- * 16 + s + wt - 1 <= 32 else 2 (pw = wt/2, s = 8*ceil(pw/8) - pw) K blocks
- * per template row, the 1-KB fragment (64 lanes x 8 fp16; lane m + 16 g holds
- * T[i][8g + 32b + q - m - s], q = 0..7, zero outside [0, wt)) of row i, block
- * b, term k (0 hi, 1 lo) of (u, c) is fragment number
- * (C * row_offset(u) + c * ht * nk) * 2 + (i * nk + b) * 2 + k; then e
- * int32[U][C].  row_offset(u) = sum over earlier units of ht * nk(wt) and
- * total_rows = that sum over all units (tmr_unit_t.row_offset, set by the
- * host); size from tmr_size(TMR_SIZE_TEMPLATE_SPLIT, U, C, total_rows).
- * prec: TMR_PREC_F16X3 writes hi and lo; the one-term precisions the hi
- * fragments only (TMR_PREC_BF16: bf16; TMR_PREC_F16: the fp16 hi). */
+ * T [h = ht][w = wt] = templates[units[u].tmpl_offset + c*h*w ...], x = t * 2^-e
+ * (one fp32 product, exact short of fp32 underflow) with 2^-e = the scale of
+ * the scale source max |T| (tmr_split_xpack's rule below: 2^-e = 2^clamp(14 -
+ * e', -63, 63) with max |T| < 2^e', so max |x| < 2^14; e = 0 for an all-zero,
+ * non-finite or > 3e38 maximum; NaN taps are ignored by the maximum), written
+ * as the kernel's MFMA A fragments over 2-D windows of 4 template rows x 8
+ * template columns:
+ *   na = ceil((h + 1) / 4) window rows, nb = ceil((w + 7 + s) / 8) window
+ *   columns, s = (-(w / 2)) mod 8 (w / 2 the integer quotient; 0 <= s < 8);
+ *   a fragment is 1024 B = 64 lanes x 8 16-bit elements, lane l at byte 16 l;
+ *   with m = l & 15 and g = l >> 4, element q = 0..7 of lane l of window
+ *   (a, b) holds T[4a + g - (m >> 3)][8b + q - (m & 7) - s], and 0 where that
+ *   index lies outside [0, h) x [0, w);
+ *   term k (0 hi, 1 lo) of window (a, b) of (u, c) is fragment number
+ *   (C * row_offset(u) + c * na * nb) * 2 + (b * na + a) * 2 + k
+ *   (column-major over the windows: the order the kernel walks them);
+ *   then the exponents e, int32[U][C], at byte C * total_rows * 2 * 1024.
+ * row_offset(u) = sum over the units before u of na * nb, and total_rows =
+ * that sum over all units (tmr_unit_t.row_offset, set by the host; the units
+ * may come in any order of sizes).  Size: tmr_size(TMR_SIZE_TEMPLATE_SPLIT, U,
+ * C, total_rows).
+ * The terms, by prec:
+ *   TMR_PREC_F16X3: hi = fp16(x rounded to TH_BITS significant bits), lo =
+ *     fp16(x - hi) (the difference in fp32).  TH_BITS is the one constant of
+ *     that name in csrc/xcorr.hip (11 as of ABI 3); "rounded
+ *     to K significant bits" is round-to-nearest-even on the fp32 bit pattern,
+ *     clearing its low 24 - K bits (inf / NaN unchanged), and K >= 11 means
+ *     the plain hi = fp16(x);
+ *   TMR_PREC_F16: hi = fp16(x); TMR_PREC_BF16: hi = bf16(x) (e is still
+ *     written and x still scaled by 2^-e).
+ *   All conversions round to nearest even.  The one-term precisions write the
+ *   hi fragments only: the contents of their lo (k = 1) slots are unspecified. */
 int tmr_template_split(const float *templates, const tmr_unit_t *units, int U, int C,
                        int64_t total_rows, int prec, void *out, void *stream);
 
@@ -187,7 +209,9 @@ int tmr_template_split(const float *templates, const tmr_unit_t *units, int U, i
 /* o [U,1,H,W] = head_bias[4] + sum_t partials[t][4];  b [U,4,H,W] (nullable) =
  * head_bias[j] + sum_t partials[t][j], t over ceil(N/tile_n) channel tiles
  * (tile_n = 128, the split kernel's tile; 64 is accepted too).  With b NULL
- * only the objectness partials (j = 4) are read.  Over a tile window of a
+ * only the objectness partials (j = 4) are read.  Each sum is fp32, over the
+ * tiles t = 0, 1, .. in order starting from +0, and the bias is added last.
+ * partials is [tile][5][U][H][W].  Over a tile window of a
  * launch (TMR_SPLIT_TILE_WINDOW): partials + first * 5*U*H*W, N = 128 * count. */
 int tmr_heads_reduce(const float *partials, int N, int tile_n, int U, int H, int W,
                      const float *head_bias, float *o, float *b, void *stream);
@@ -205,18 +229,51 @@ int tmr_heads_reduce(const float *partials, int N, int tile_n, int U, int H, int
  *                   normwise contract (config B);
  *   TMR_PREC_BF16:  one bf16 term, fp32 accumulation (config C, 1e-2 contract);
  *   TMR_PREC_F16:   one scaled fp16 term.
+ * Scale sources and scales.  A scale source is a float m >= 0, normally a
+ * max |.|; its scale is split_scale(m) = 2^clamp(14 - e, -63, 63) with e the
+ * integer with 2^(e-1) <= m < 2^e (so m * scale < 2^14; the clamp keeps the
+ * product of an activation and a weight scale a normal fp32 number).  A
+ * source that is 0, negative, NaN, infinite or above 3e38 gives scale 1.
+ * TMR_PREC_BF16 uses no scales (scale 1; the scale pointers may be NULL).
  * tmr_absmax_rows: out[s] = max |x[s][0..n)| for x [S][n] (or max(out[s], ...)
- * when accumulate), the scale sources for the packs and the conv (F16X3 /
- * F16; NULL allowed for BF16).  tmr_scale_merge: out_img[b] = max(img_max[b] (nullable: 0),
+ * when accumulate; S < 65536; n = 0 gives 0, or leaves out[s] when accumulate;
+ * any alignment of x), the scale sources for the packs and the conv (F16X3 /
+ * F16; NULL allowed for BF16).  tmr_pixel_absmax (below) likewise per pixel.
+ * Both ignore NaN elements (a row or pixel of NaNs alone gives 0), return
+ * +inf when an element is +-inf, and +0 for -0.0; with accumulate, out[s]
+ * must hold a non-negative float (it is compared as an unsigned bit pattern).
+ * tmr_scale_merge: out_img[b] = max(0, img_max[b] (nullable: absent),
  * unit_max[u] over the units with unit_image[u] == b), out_unit[u] =
- * out_img[unit_image[u]] (out_img nullable) -- one scale per image for a
- * launch whose tiles read an image's src0 records and its units' src1
- * records together.
- * tmr_split_xpack: x [S][C][H][W] fp32 -> [S][ceil(C/32)*halves][Hp][Wp][64 B]
- * (halves 2 for F16X3: hi, lo), zero padded to whole 16x32 tiles plus the ks
- * halo (size TMR_SIZE_XPACK).  `up` bit TMR_XPACK_UPSAMPLE: the records are
- * of up2x(x) (H, W are x's; the records' are 2H, 2W); bit TMR_XPACK_ONES: a
- * constant-1 channel is appended (C + 1 channels; see tmr_split_fold_proj).
+ * out_img[unit_image[u]] (out_img nullable: only out_unit is written) -- one
+ * scale per image for a launch whose tiles read an image's src0 records and
+ * its units' src1 records together.  unit_image may be in any order and any
+ * U; an image without units receives max(0, img_max[b]), i.e. 0 when img_max
+ * is NULL; out_unit[u] of a unit whose image lies outside [0, B) is not written.
+ * tmr_split_xpack: x [S][C][H][W] fp32 -> planar 16-B pieces
+ *   [S][NC = ceil(C/32) chunks][halves][4 pieces q][Hp][Wp][8 x 16 bit]
+ * (halves 2 for F16X3: hi then lo; 1 otherwise), Hp = ceil(H/16)*16 + ks - 1,
+ * Wp = ceil(W/32)*32 + ks - 1 (whole 16x32 tiles plus the ks halo; size
+ * TMR_SIZE_XPACK = S * NC * halves * Hp * Wp * 64 bytes).  Element j of piece
+ * q of chunk c at padded (yp, xp) is channel 32c + 8q + j of pixel (yp - ks/2,
+ * xp - ks/2); channels >= C and pixels outside the image are zero in every
+ * term.  With v = x * scale (one fp32 product): F16X3 hi = fp16(v), lo =
+ * fp16(v - hi) (the difference in fp32); F16 fp16(v); BF16 bf16(x); all
+ * round to nearest even.  In every record and fragment of this header the
+ * sign of the zero terms of a -0.0 input is unspecified: they may be stored
+ * as +0 or as -0 (the compiler may fuse the scaling and the conversion into
+ * one multiply-add with a +0 addend, for some elements of a piece and not
+ * for others); a zero operand adds the same to every non-zero sum either
+ * way.  Every other term, negative values that round to -0 included, is as
+ * stated.  `up` bit TMR_XPACK_UPSAMPLE: the records are
+ * of up2x(x) (tmr_upsample2x's values bit for bit; H, W are x's; the records',
+ * and those in the formulas above, are 2H, 2W); bit TMR_XPACK_ONES: a
+ * constant-1 channel is appended as channel C (C + 1 channels in the formulas
+ * above; see tmr_split_fold_proj): 1 inside the image, 0 in the padding, so
+ * its hi element is fp16(1 * scale) (lo 0).  The caller keeps that finite: the
+ * scale source must be >= 0.25 (scale <= 2^15; a smaller source gives
+ * scale >= 2^16 and an infinite fp16), e.g. max(max |x|, 1), the maximum
+ * over the appended channel too; a source of 2^38 or more (scale <= 2^-25)
+ * rounds the channel to 0.
  * xmax_per_sample = 0: one scale source *xmax for
  * every sample; 1: xmax[s] for sample s (float[S]); 2: xmax[s][y][x] per
  * (output-resolution) pixel, for TMR_SPLIT_XMAX_PER_PIXEL 1x1 convs.
@@ -224,12 +281,23 @@ int tmr_heads_reduce(const float *partials, int N, int tile_n, int U, int H, int
  * of the batch: its hi/lo parts never go subnormal because another sample is
  * 2^20 larger (a power-of-two rescale is exact otherwise, so results equal
  * the single-unit run's bit for bit).
- * tmr_split_wpack: w [N][C0+C1][ks][ks] -> [ks*ks][ceil(C0/32)+ceil(C1/32)]
- * [ceil(N/128)*128][rec]; the conv's src0 (per image, C0 channels, packed by
- * xpack with S = images) and src1 (per unit, C1) may both be present.
- * Records: one 64-B record per pixel per 32-channel chunk (F16X3: a hi and a
- * lo record); weights [ks*ks][chunks][ceil(N/128)*128][128 B (wh, wl) |
- * 64 B].  Head partials use 128-channel tiles (tmr_heads_reduce tile_n = 128). */
+ * tmr_split_wpack: w [N][C0+C1][ks][ks] -> planar 16-B pieces
+ *   [tap = ky*ks + kx][chunk][plane][Npad = ceil(N/128)*128][8 x 16 bit];
+ * the conv's src0 (per image, C0 channels, packed by xpack with S = images)
+ * and src1 (per unit, C1) may both be present, and each is padded to whole
+ * 32-channel chunks by itself: chunks 0 .. NC0-1 (NC0 = ceil(C0/32)) are
+ * src0's, element j of piece q of chunk c being input channel 32c + 8q + j
+ * (zero from C0 on); chunks NC0 .. NC0+NC1-1 (NC1 = ceil(C1/32)) are src1's,
+ * input channel C0 + 32(c - NC0) + 8q + j (zero from C0 + C1 on).  Planes:
+ * 4 hi pieces q = 0..3, then for F16X3 4 lo pieces (8 planes; 4 otherwise).
+ * Rows n >= N are zero.  Size TMR_SIZE_WPACK = ks*ks * (NC0+NC1) * Npad *
+ * (128 | 64) bytes.  With v = w * split_scale(*wmax) (one fp32 product):
+ * F16X3 wh = fp16(v rounded to WH_BITS significant bits), wl = fp16(v - wh)
+ * (the difference in fp32) -- WH_BITS is the one constant of that name in
+ * csrc/conv_split.hip (8 as of ABI 3), "rounded to K
+ * significant bits" as under tmr_template_split; F16 fp16(v); BF16 bf16(w).
+ * The activations' hi part is always the plain fp16(v).
+ * Head partials use 128-channel tiles (tmr_heads_reduce tile_n = 128). */
 #define TMR_PREC_F16X3 0
 #define TMR_PREC_BF16 1
 #define TMR_PREC_F16 2
@@ -241,16 +309,19 @@ int tmr_scale_merge(const float *img_max, const float *unit_max, const int32_t *
 int tmr_split_xpack(const float *x, int S, int C, int H, int W, int up, int ks, int prec,
                     const float *xmax, int xmax_per_sample, void *out, void *stream);
 /* tmr_split_xpack16: the TMR_PREC_BF16 records of a bf16 x [S][C][H][W]
- * (tmr_xcorr's bf16 f_TM; W % 8 == 0): bit-identical to tmr_split_xpack
- * of the fp32 values those bf16 elements round. */
+ * (tmr_xcorr's bf16 f_TM; W % 8 == 0) in tmr_split_xpack's planar layout,
+ * size and padding: bit-identical to tmr_split_xpack of the fp32 values
+ * those bf16 elements round. */
 int tmr_split_xpack16(const void *x, int S, int C, int H, int W, int ks, int prec, void *out,
                       void *stream);
 /* tmr_split_fold_proj: with tmr_split_xpack's TMR_XPACK_UPSAMPLE | ONES
  * records of the SAM features it feeds the decoder's fp half without
  * materialising fp: conv(input_proj(x))
  * = conv'([x; 1]), W'[n][c] = sum_k Wd[n][k] P[k][c], W'[n][Cin] = sum_k
- * Wd[n][k] b[k] per tap (matching_net.py:27-30,56,63-69), fp64 accumulation;
- * out [N][Cin+1][ks][ks] from wd [N][Cw][ks][ks] (first Cp channels = fp). */
+ * Wd[n][k] b[k] per tap (matching_net.py:27-30,56,63-69), each sum accumulated
+ * in fp64 over k = 0 .. Cp-1 ascending from 0 and rounded once to fp32;
+ * out [N][Cin+1][ks][ks] from wd [N][Cw][ks][ks] (first Cp channels = fp),
+ * proj_w [Cp][Cin], proj_b [Cp]. */
 int tmr_split_fold_proj(const float *wd, int N, int Cw, int Cp, int ks, const float *proj_w,
                         const float *proj_b, int Cin, float *out, void *stream);
 int tmr_split_wpack(const float *w, int N, int C0, int C1, int ks, int prec, const float *wmax,
@@ -304,7 +375,8 @@ int tmr_split_wpack(const float *w, int N, int C0, int C1, int ks, int prec, con
 #define TMR_SPLIT_TILE_COUNT_SHIFT 24
 #define TMR_SPLIT_TILE_WINDOW(first, count) \
     (((first) << TMR_SPLIT_TILE_FIRST_SHIFT) | ((count) << TMR_SPLIT_TILE_COUNT_SHIFT))
-/* out[s][p] = max_c |x[s][c][p]| for x [S][C][HW] */
+/* out[s][p] = max_c |x[s][c][p]| for x [S][C][HW], any C >= 1 (NaN, inf and
+ * -0.0 as tmr_absmax_rows: see "Scale sources and scales" above) */
 int tmr_pixel_absmax(const float *x, int S, int C, int64_t HW, float *out, void *stream);
 int tmr_split_conv(const void *xp0, int C0, const int32_t *unit_image, const void *xp1, int C1, int U,
                    int H, int W, int ks, int prec, const void *wpack, const float *wmax, const float *xmax,

@@ -66,9 +66,10 @@ def test_size_queries_no_gpu():
 
 def test_split_size_queries_no_gpu():
     """Byte sizes of the split-kernel records (include/tmr.h): activations
-    padded to whole 16x32 tiles plus the ks halo, one 64-B record per pixel per
-    32-channel chunk and half (fp32 3-term: hi and lo halves); weights
-    [ks^2][chunks][ceil(N/128)*128][128 B (wh, wl) | 64 B]."""
+    padded to whole 16x32 tiles plus the ks halo, 64 B (four planar 16-B
+    pieces) per pixel per 32-channel chunk and half (fp32 3-term: hi and lo
+    halves); weights ks^2 * chunks * ceil(N/128)*128 * (128 B: 4 hi + 4 lo
+    planes | 64 B)."""
     assert _size("xpack", 2, 512, 128, 128, 3, 0) == 2 * 32 * 130 * 130 * 64
     assert _size("xpack", 2, 512, 128, 128, 3, 1) == 2 * 16 * 130 * 130 * 64
     assert _size("xpack", 1, 257, 17, 33, 1, 0) == 1 * 9 * 2 * 32 * 64 * 64

@@ -16,6 +16,7 @@ import torch
 
 import oracle
 import tmr_amd
+from operand_ref import xrecords_ref as _xrecords_ref
 from tmr_amd import host, synth
 
 pytestmark = pytest.mark.gpu
@@ -292,32 +293,6 @@ def test_upsample2x_tiled_and_projection_order(Hin, Win):
     eng = tmr_amd.TMREngine({k: cuda(v) for k, v in P.items()}, tmr_amd.PathConfig(emb_dim=40))
     fp, _ = eng.project(fd)
     assert normwise(fp.cpu().numpy(), ref.numpy()) <= TOL
-
-
-def _xrecords_ref(x, ks, prec, xmax):
-    """tmr_split_xpack's record layout restated in torch: [s][chunk][half]
-    [piece q][Hp][Wp][8 x 16-bit], hi = fl16(x s), lo = fl16(x s - hi) (F16X3),
-    s = 2^(14 - e) with max|x| < 2^e (conv_split.hip split_scale), zero ring."""
-    S, C, H, W = x.shape
-    NCc, pad = (C + 31) // 32, ks // 2
-    Hp, Wp = -(-H // 16) * 16 + ks - 1, -(-W // 32) * 32 + ks - 1
-    xs = torch.zeros(S, NCc * 32, Hp, Wp, dtype=torch.float32, device=x.device)
-    sc = 1.0
-    if prec != "bf16":  # one source, one per sample [S] or one per pixel [S,H,W]
-        m = np.asarray(xmax, np.float32)
-        e = np.frexp(m)[1]
-        sc = np.where(m > 0, np.exp2(np.clip(14 - e, -63, 63)), 1.0).astype(np.float32)
-        sc = torch.from_numpy(sc.reshape((S, 1, H, W) if m.ndim == 3 else (-1, 1, 1, 1) if m.ndim else ()))
-        sc = sc.to(x.device)
-    xs[:, :C, pad:pad + H, pad:pad + W] = x * sc
-    dt = torch.bfloat16 if prec == "bf16" else torch.float16
-    hi = xs.to(dt)
-    halves = [hi]
-    if prec == "fp32":
-        halves.append((xs - hi.float()).to(dt))
-    # [S][NCc][32][Hp][Wp] -> [S][NCc][P=4][Hp][Wp][8]
-    recs = [h.view(S, NCc, 4, 8, Hp, Wp).permute(0, 1, 2, 4, 5, 3) for h in halves]
-    return torch.stack(recs, 2).contiguous().view(torch.int16).flatten()
 
 
 @pytest.mark.parametrize("S,C,H,W,ks", [(2, 40, 19, 36, 3), (1, 64, 128, 128, 3), (3, 33, 8, 12, 1),
