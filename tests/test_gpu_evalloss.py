@@ -67,39 +67,51 @@ def test_golden_cases_dropin_and_fused(cases):
     """Every fixture case through GT_map.Get_pred_gts + SetCriterion_TM (ABI
     phases ASSIGN, GATHER, ROWS) and through eval_loss (ASSIGN | LOSS)."""
     for c in cases:
-        tag = f"case {c['index']}"
-        args = SimpleNamespace(positive_threshold=c["pt"], negative_threshold=c["nt"],
-                               ablation_no_box_regression=c["a"], focal_loss=c["focal"])
-        po = [cuda(L["o"]) for L in c["lv"]]
-        pr = [cuda(L["reg"]) for L in c["lv"]]
-        gtb = [cuda(b) for b in c["boxes"]]
-        ex = [cuda(c["exemplars"][b:b + 1]) for b in range(c["B"])]
-        preds, gts, maps = tmr_amd.GT_map(args).Get_pred_gts(po, pr, gtb, ex, _batch(c))
-        assert set(preds) == {"objectness", "regressions"}
-        assert set(gts) == {"objectness", "regressions", "weight_objectness", "weight_regressions"}
-        for lv, L in enumerate(c["lv"]):
-            assert maps[lv].dtype == torch.float32 and bits_equal(maps[lv].cpu().numpy(), L["gt_map"]), tag
-            assert bits_equal(preds["objectness"][lv].cpu().numpy(), L["pred_obj"]), tag
-            assert bits_equal(preds["regressions"][lv].cpu().numpy(), L["pred_reg"]), tag
-            assert bits_equal(gts["objectness"][lv].cpu().numpy(), L["gt_obj"]), tag
-            assert bits_equal(gts["regressions"][lv].cpu().numpy(), L["gt_reg"]), tag
-            assert gts["weight_objectness"][lv] is None and gts["weight_regressions"][lv] is None
-        loss = tmr_amd.build_criterion(args)(preds, gts)
-        assert set(loss) == {"loss_ce", "loss_giou"}
-        fused = tmr_amd.TMREngine.eval_loss(
-            po, pr, np.arange(c["B"]), c["exemplars"], c["boxes"], positive_threshold=c["pt"],
-            negative_threshold=c["nt"], focal=c["focal"], ablation_no_box_regression=c["a"],
-            regression_scaling_imgsize=c["b"], regression_scaling_WH_only=c["c"])
-        rce, rgi = _ref_losses(c)
-        for name, d in (("drop-in", loss), ("fused", fused)):
-            for k, gold, ref in (("loss_ce", c["loss"][0], rce), ("loss_giou", c["loss"][1], rgi)):
-                v = d[k]
-                assert v.dtype == torch.float32 and v.dim() == 0 and not v.requires_grad
-                print(f"{tag} {name} {k}: got {float(v):.9g} golden {float(gold):.9g} float64 {ref:.12g}")
-                assert close(v, gold, REL), (tag, name, k, float(v), float(gold))
-                assert close(v, ref, REL), (tag, name, k, float(v), ref)
-        for lv, L in enumerate(c["lv"]):
-            assert bits_equal(fused["gt_map"][lv].cpu().numpy(), L["gt_map"]), tag
+        run_golden_case(c)
+
+
+def run_golden_case(c, put=cuda):
+    """One fixture case with every assertion of test_golden_cases_dropin_and_fused;
+    returns the outputs as host arrays (put: how an input reaches the device)."""
+    tag = f"case {c['index']}"
+    args = SimpleNamespace(positive_threshold=c["pt"], negative_threshold=c["nt"],
+                           ablation_no_box_regression=c["a"], focal_loss=c["focal"])
+    po = [put(L["o"]) for L in c["lv"]]
+    pr = [put(L["reg"]) for L in c["lv"]]
+    gtb = [put(b) for b in c["boxes"]]
+    ex = [put(c["exemplars"][b:b + 1]) for b in range(c["B"])]
+    preds, gts, maps = tmr_amd.GT_map(args).Get_pred_gts(po, pr, gtb, ex, _batch(c))
+    assert set(preds) == {"objectness", "regressions"}
+    assert set(gts) == {"objectness", "regressions", "weight_objectness", "weight_regressions"}
+    for lv, L in enumerate(c["lv"]):
+        assert maps[lv].dtype == torch.float32 and bits_equal(maps[lv].cpu().numpy(), L["gt_map"]), tag
+        assert bits_equal(preds["objectness"][lv].cpu().numpy(), L["pred_obj"]), tag
+        assert bits_equal(preds["regressions"][lv].cpu().numpy(), L["pred_reg"]), tag
+        assert bits_equal(gts["objectness"][lv].cpu().numpy(), L["gt_obj"]), tag
+        assert bits_equal(gts["regressions"][lv].cpu().numpy(), L["gt_reg"]), tag
+        assert gts["weight_objectness"][lv] is None and gts["weight_regressions"][lv] is None
+    loss = tmr_amd.build_criterion(args)(preds, gts)
+    assert set(loss) == {"loss_ce", "loss_giou"}
+    fused = tmr_amd.TMREngine.eval_loss(
+        po, pr, np.arange(c["B"]), c["exemplars"], c["boxes"], positive_threshold=c["pt"],
+        negative_threshold=c["nt"], focal=c["focal"], ablation_no_box_regression=c["a"],
+        regression_scaling_imgsize=c["b"], regression_scaling_WH_only=c["c"])
+    rce, rgi = _ref_losses(c)
+    for name, d in (("drop-in", loss), ("fused", fused)):
+        for k, gold, ref in (("loss_ce", c["loss"][0], rce), ("loss_giou", c["loss"][1], rgi)):
+            v = d[k]
+            assert v.dtype == torch.float32 and v.dim() == 0 and not v.requires_grad
+            print(f"{tag} {name} {k}: got {float(v):.9g} golden {float(gold):.9g} float64 {ref:.12g}")
+            assert close(v, gold, REL), (tag, name, k, float(v), float(gold))
+            assert close(v, ref, REL), (tag, name, k, float(v), ref)
+    for lv, L in enumerate(c["lv"]):
+        assert bits_equal(fused["gt_map"][lv].cpu().numpy(), L["gt_map"]), tag
+    host_ = lambda xs: [x.cpu().numpy() for x in xs]  # noqa: E731
+    return dict(maps=host_(maps), pred_obj=host_(preds["objectness"]), pred_reg=host_(preds["regressions"]),
+                gt_obj=host_(gts["objectness"]), gt_reg=host_(gts["regressions"]),
+                loss=[loss[k].cpu().numpy() for k in ("loss_ce", "loss_giou")],
+                fused=[fused[k].cpu().numpy() for k in ("loss_ce", "loss_giou", "sums", "counts", "target")],
+                fused_maps=host_(fused["gt_map"]))
 
 
 # ---------------------------------------------------------------- seeded sweep
@@ -153,11 +165,11 @@ def _ref_units(cfg):
     return units, out
 
 
-def _assign(cfg, units, sel=None, with_loss=True):
+def _assign(cfg, units, sel=None, with_loss=True, put=cuda):
     """TMR_GT_ASSIGN | TMR_GT_LOSS over `units`, the descriptors of the maps
     `sel` (default all)."""
     sel = np.arange(len(cfg["ui"])) if sel is None else np.asarray(sel)
-    return gl.assign(cuda(cfg["o"][sel]), None if cfg["a"] else cuda(cfg["reg"][sel]), units, cfg["boxes"],
+    return gl.assign(put(cfg["o"][sel]), None if cfg["a"] else put(cfg["reg"][sel]), units, cfg["boxes"],
                      cfg["pt"], cfg["nt"], cfg["last"], cfg["focal"], with_loss=with_loss)
 
 
@@ -167,11 +179,18 @@ SWEEP.append((128, 128, 300))
 
 @pytest.mark.parametrize("k", range(len(SWEEP)))
 def test_sweep_against_restatement(k):
+    run_sweep(k)
+
+
+def run_sweep(k, put=cuda, fused=False):
+    """SWEEP[k] with every assertion of test_sweep_against_restatement, and the
+    same case through the fused eval_loss (the batch as one group, against the
+    restatement at REL); returns the outputs as host arrays."""
     H, W, G = SWEEP[k]
     NI, E = (2, 2) if H == 128 else (1 + k % 3, 1 + (k // 3) % 3)
     cfg = _sweep_case(100 + k, H, W, G, NI, E)
     units, ref = _ref_units(cfg)
-    st = _assign(cfg, units)
+    st = _assign(cfg, units, put=put)
     obj, lab, rp, rg, counts = gl.gather(st)
     gm, tg, sums = st.gt_map.cpu().numpy(), st.target.cpu().numpy(), st.sums.cpu().numpy()
     so = ro = 0
@@ -198,6 +217,19 @@ def test_sweep_against_restatement(k):
     ce, gi = gl.group_losses(st.sums, st.counts, None)
     for got in ((rows[0], rows[1]), (ce, gi)):
         assert close(got[0], rce, REL) and close(got[1], rgi, REL), (SWEEP[k], got, rce, rgi)
+    out = dict(gt_map=gm, target=tg, sums=sums, counts=counts, obj=obj.cpu().numpy(), lab=lab.cpu().numpy(),
+               rp=rp.cpu().numpy(), rg=rg.cpu().numpy(), rows=rows, ce=ce.cpu().numpy(), gi=gi.cpu().numpy())
+    if fused:  # the same case through the fused entry point (one level: it is the last)
+        f = tmr_amd.TMREngine.eval_loss(
+            put(cfg["o"]), None if cfg["a"] else put(cfg["reg"]), cfg["ui"], cfg["ex"], cfg["boxes"],
+            positive_threshold=cfg["pt"], negative_threshold=cfg["nt"], focal=cfg["focal"],
+            ablation_no_box_regression=cfg["a"], regression_scaling_imgsize=cfg["b"],
+            regression_scaling_WH_only=cfg["c"])
+        assert cfg["last"], "eval_loss treats its one level as the last"
+        assert close(f["loss_ce"], rce, REL) and close(f["loss_giou"], rgi, REL), \
+            (SWEEP[k], float(f["loss_ce"]), rce, float(f["loss_giou"]), rgi)
+        out["fused"] = [f[n].cpu().numpy() for n in ("loss_ce", "loss_giou", "gt_map", "sums", "counts", "target")]
+    return out
 
 
 def test_batch_independence_and_repeat():

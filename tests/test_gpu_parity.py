@@ -493,21 +493,30 @@ def test_custom_shape_maxpool_vs_reference(shape):
     """Bit-exact against the reference formulation for every adaptive
     kernel shape (plus an off-centre one): negatives (the zero padding
     wins at the border), exact ties, +-0 and a NaN."""
+    run_maxpool(shape)
+
+
+def run_maxpool(shape, put=lambda t: t.to(DEV)):
+    """The body of test_custom_shape_maxpool_vs_reference; returns the GPU
+    results per kernel shape (put: how the input reaches the device)."""
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.round(torch.randn(shape, generator=g) * 4) / 4  # many exact ties
     x.view(-1)[::7] = -x.view(-1)[::7].abs() - 1
     if x.numel() > 20:
         x.view(-1)[5] = -0.0
         x.view(-1)[11] = float("nan")
+    outs = []
     for k in KERNELS:
         ref = _maxpool_reference(x, k)
-        got = tmr_amd.custom_shape_3x3_maxpool2d(x.to(DEV), k).cpu()
+        got = tmr_amd.custom_shape_3x3_maxpool2d(put(x), k).cpu()
         assert got.shape == ref.shape
         assert torch.equal(torch.isnan(got), torch.isnan(ref)), k
         m = ~torch.isnan(ref)
         assert torch.equal(got[m], ref[m]), k
+        outs.append(got.numpy())
     with pytest.raises(tmr_amd.TMRError):
-        tmr_amd.custom_shape_3x3_maxpool2d(x.to(DEV), [[0] * 3] * 3)
+        tmr_amd.custom_shape_3x3_maxpool2d(put(x), [[0] * 3] * 3)
+    return outs
 
 
 @pytest.mark.parametrize("name", ["pred_boxes", "pred_boxes_nonfinite"])

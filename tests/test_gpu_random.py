@@ -71,6 +71,15 @@ def draw(seed):
 
 @pytest.mark.parametrize("seed", range(N_CONFIG))
 def test_random_config_vs_oracle(seed):
+    run_config(seed)
+
+
+def run_config(seed, alloc=None, setup=None):
+    """One drawn configuration through detect() and forward_units() with every
+    assertion of test_random_config_vs_oracle; returns the outputs (host
+    arrays) and the engine's route record.  alloc (tests/guarded_alloc.py)
+    places the features; setup(eng) adjusts the fresh engine before its first
+    call (tests/test_gpu_guarded.py)."""
     c = draw(seed)
     P = synth.reference_state_dict(300 + seed, cin=c["cin"], emb=c["emb"], obj_bias=c["bias"])
     P["matcher.scale"] = torch.tensor([c["scale"]])
@@ -81,8 +90,12 @@ def test_random_config_vs_oracle(seed):
     prec = c["precision"]
     eng = tmr_amd.TMREngine({k: v.to(DEV) for k, v in P.items()},
                             tmr_amd.PathConfig(emb_dim=c["emb"], precision=prec))
-    fd = torch.from_numpy(feats).to(DEV)
+    if setup is not None:
+        setup(eng)
+    fd = torch.from_numpy(feats).to(DEV) if alloc is None else alloc.place(feats)
     L, Bx, R = eng.detect(fd, ex, cls_ths=c["cls"], iou_threshold=c["iou"])
+    route = dict(xcorr=eng.last_xcorr_algo, out16=eng.last_xcorr_out16, box_route=eng.last_box_route,
+                 points=eng.last_points, graph=eng.last_graph)
     ui = np.repeat(np.arange(B), E)
     r = eng.forward_units(fd, ui, ex.reshape(-1, 4))
     o, b = r["o"].cpu().numpy(), r["b"].cpu().numpy()
@@ -112,6 +125,8 @@ def test_random_config_vs_oracle(seed):
             agreement.check(agreement.compare(omaps, gmaps, list(ex[img]), c["cls"], c["iou"]))
     print(f"seed {seed}: {c} xcorr={eng.last_xcorr_algo} kept={[int(x.shape[0]) for x in L]} "
           f"worst normwise {worst:.2e}")
+    return dict(config=c, route=route, o=o, b=b, L=[x.cpu().numpy() for x in L], Bx=[x.cpu().numpy() for x in Bx],
+                R=[x.cpu().numpy() for x in R])
 
 
 class _Passthrough(torch.nn.Module):
@@ -159,7 +174,10 @@ def test_cancellation_variant_margin():
     _module_variant(188, 5e-6)
 
 
-def _module_variant(seed, tol):
+def _module_variant(seed, tol, alloc=None, setup=None):
+    """One drawn module configuration against the oracle; returns the module's
+    outputs as host arrays.  alloc / setup: as run_config (setup(model) runs on
+    the module once it is on the device)."""
     from types import SimpleNamespace
     c = draw_variant(seed)
     args = SimpleNamespace(emb_dim=c["emb"], fusion=c["fusion"], ablation_no_box_regression=not c["box_reg"],
@@ -178,8 +196,11 @@ def _module_variant(seed, tol):
     feats = synth.sam_features(800 + seed, c["B"], c["cin"], c["hf"], c["wf"])
     H, W = (2 * c["hf"], 2 * c["wf"]) if c["upsample"] else (c["hf"], c["wf"])
     ex, _ = synth.exemplar_set(900 + seed, c["B"], 1, H, W, 1, min(9, 2 * (min(H, W) // 4) + 1))
+    if setup is not None:
+        setup(model)
+    put = (lambda a: torch.from_numpy(a).to(DEV)) if alloc is None else alloc.place
     with torch.no_grad():
-        os_, bs_, ftm, f0 = model(torch.from_numpy(feats).to(DEV), [torch.from_numpy(e).to(DEV) for e in ex])
+        os_, bs_, ftm, f0 = model(put(feats), [put(e) for e in ex])
     ro, rb, rf, r0 = oracle.forward_torch(torch.from_numpy(feats), [torch.from_numpy(e) for e in ex], P,
                                           feature_upsample=c["upsample"], fusion=c["fusion"],
                                           squeeze=c["squeeze"], box_reg=c["box_reg"],
@@ -192,3 +213,5 @@ def _module_variant(seed, tol):
     assert max(errs) <= tol, (c, errs)
     assert normwise(f0.cpu().numpy(), r0.numpy()) <= 1e-6, c
     print(f"variant seed {seed}: {c} worst normwise {max(errs):.2e}")
+    return dict(config=c, graph=model.engine().last_graph, o=os_[0].cpu().numpy(),
+                b=bs_[0].cpu().numpy() if c["box_reg"] else None, f_tm=ftm[0].cpu().numpy(), f0=f0.cpu().numpy())

@@ -172,7 +172,13 @@ def test_feature_stats_vs_mapper_numpy(B, C, H, W):
     f = synth.sam_features(11, B, C, H, W) if B else np.zeros((0, C, H, W), np.float32)
     if B:
         f[:, :, 0, 0] = 0.0  # exact zeros count as sparse (<= 0)
-    got = mr.feature_stats(torch.from_numpy(f).to(DEV))
+    check_feature_stats(f, mr.feature_stats(torch.from_numpy(f).to(DEV)))
+
+
+def check_feature_stats(f, got):
+    """The assertions of test_feature_stats_vs_mapper_numpy on one batch's
+    statistics (shared with tests/test_gpu_guarded.py)."""
+    B = f.shape[0]
     assert got.shape == (B, 4)
     for b in range(B):
         m, s, x, p = oracle.mapper_stats(f[b])
