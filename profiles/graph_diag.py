@@ -26,7 +26,7 @@ for i in range(4):
     units = host.build_units(ex.reshape(-1, 4), ui, 2 * hf, 2 * hf, emb)[0]
     sigs.append(eng._graph_signature(feats, units, ui, False, False))
     eng.detect(feats, ex, 0.5, 0.5)
-    print(i, eng.last_graph, eng.last_graph_error, list(eng._graph_seen.values()), flush=True)
+    print(i, eng.last_graph, eng.last_graph_error, list(eng._graphs.seen.values()), flush=True)
 for i in range(1, len(sigs)):
     if sigs[i] is None or sigs[0] is None:
         print("sig None", i)

@@ -26,7 +26,7 @@ from tmr_import import load_package  # noqa: E402
 tmr = load_package()
 from tmr_amd import synth  # noqa: E402
 from tmr_amd._lib import PREC_CODES, call, load, ptr, stream  # noqa: E402
-from tmr_amd.engine import absmax, pack_split_w, pack_split_x  # noqa: E402
+from tmr_amd.operands import absmax, pack_split_w, pack_split_x  # noqa: E402
 
 
 def main():

@@ -73,7 +73,7 @@ def main():
     heat = None
     if a.heat_units:
         from tmr_amd._lib import PREC_CODES, call, ptr, stream
-        from tmr_amd.engine import absmax, pack_split_w, pack_split_x
+        from tmr_amd.operands import absmax, pack_split_w, pack_split_x
         hw_ = torch.randn((2048, 512, 3, 3), device=dev, generator=g) * 0.01
         hx = torch.randn((a.heat_units, 512, H, H), device=dev, generator=g)
         hwp, hwmax = pack_split_w(hw_, 512, "fp32")

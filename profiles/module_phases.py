@@ -25,7 +25,7 @@ sys.path.insert(0, REPO)
 from tmr_import import load_package  # noqa: E402
 
 tmr = load_package()
-from tmr_amd import engine as E_, synth  # noqa: E402
+from tmr_amd import engine as E_, graphs as G_, synth  # noqa: E402
 
 STAMPS = []
 
@@ -66,7 +66,7 @@ def main():
     ex, _ = synth.exemplar_set(2000, 1, E, 128, 128, 7, 15)
     dummy = {"regression_ablation_b": False, "regression_ablation_c": False}
 
-    peaks0, nms0, replay0 = E_.TMREngine.peaks, E_.TMREngine.nms, E_._DetectGraph.replay
+    peaks0, nms0, replay0 = E_.TMREngine.peaks, E_.TMREngine.nms, G_._ForwardGraph.replay
 
     def peaks(*args, **kw):
         r = peaks0(*args, **kw)
@@ -86,7 +86,7 @@ def main():
 
     E_.TMREngine.peaks = staticmethod(peaks)
     E_.TMREngine.nms = staticmethod(nms)
-    E_._DetectGraph.replay = replay
+    G_._ForwardGraph.replay = replay
 
     def image(b):
         stamp("img")

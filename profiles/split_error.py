@@ -13,7 +13,7 @@ sys.path.insert(0, REPO)
 from tmr_import import load_package  # noqa: E402
 
 load_package()
-from tmr_amd.engine import conv2d_split  # noqa: E402
+from tmr_amd.operands import conv2d_split  # noqa: E402
 
 dev = torch.device("cuda:0")
 worst = {}

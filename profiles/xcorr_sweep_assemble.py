@@ -13,7 +13,7 @@ Per (regime, algo, k): the kernel-trace duration (ms per launch), the HBM bytes
 moved (2 x FETCH_SIZE + WRITE_SIZE, MI355X_MICROARCH.md), their rate against
 the 8 TB/s peak, MFMA busy (SQ_VALU_MFMA_BUSY_CYCLES over 1024 SIMDs x the
 per-XCD GPU cycles), VALU instructions and the effective clock.  The crossover
-rule (engine.xcorr_choice) takes the per-k launch durations of this table; the
+rule (xcorr_cost.xcorr_choice) takes the per-k launch durations of this table; the
 counters say which roof binds each point (hbm_frac near 0.8 of peak = HBM bound,
 i.e. the ~6.3 TB/s achievable; rising VALU instructions and falling HBM rate =
 compute bound).

@@ -203,35 +203,26 @@ def size(kind: str, *dims) -> int:
     return n
 
 
-def xcorr(**fields) -> None:
-    """tmr_xcorr with a tmr_xcorr_args_t built from keyword fields (pointer
-    fields take ptr(...) values or None; omitted fields are 0 / NULL)."""
-    a = XcorrArgs()
-    for k, v in fields.items():
-        if k == "stream":
-            continue
-        setattr(a, k, v if v is not None else (None if k in _XPTR else 0))
-    check(load().tmr_xcorr(ctypes.byref(a), fields.get("stream")), "tmr_xcorr")
-
-
-_XPTR = {"f", "templates", "units", "img_units", "scale", "out", "relu_out", "work", "out_absmax", "tmpl_split"}
-
-
-_GT_FIELDS = {n for n, _ in GtLossArgs._fields_} - {"pad_"}
-
-
-def gt_loss_args(**fields) -> GtLossArgs:
-    """A tmr_gt_loss_args_t from keyword fields (pointer fields take ptr(...)
-    values or None; omitted fields are 0 / NULL).  A name the struct does not
-    have is an error, never silently dropped."""
-    unknown = set(fields) - _GT_FIELDS
+def _fill(struct, what: str, fields: dict):
+    """A ctypes.Structure from keyword fields (pointer fields take ptr(...) or None; omitted and
+    None fields are 0 / NULL).  A name the struct lacks is an error, never a Python attribute."""
+    unknown = set(fields) - {n for n, _ in struct._fields_ if n != "pad_"}
     if unknown:
-        raise TMRError(f"tmr_gt_loss_args_t has no field(s) {sorted(unknown)}")
-    a = GtLossArgs()
+        raise TMRError(f"{what} has no field(s) {sorted(unknown)}")
+    a = struct()
     for k, v in fields.items():
         if v is not None:
             setattr(a, k, v)
     return a
+
+
+def xcorr(stream=None, **fields) -> None:
+    """tmr_xcorr(&args, stream) with a tmr_xcorr_args_t from keyword fields."""
+    check(load().tmr_xcorr(ctypes.byref(_fill(XcorrArgs, "tmr_xcorr_args_t", fields)), stream), "tmr_xcorr")
+
+
+def gt_loss_args(**fields) -> GtLossArgs:
+    return _fill(GtLossArgs, "tmr_gt_loss_args_t", fields)
 
 
 def gt_loss(stream_=None, **fields) -> None:

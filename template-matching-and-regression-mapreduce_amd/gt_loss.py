@@ -16,11 +16,7 @@ import torch
 from . import exp_table, host
 from ._lib import (GT_ASSIGN, GT_GATHER, GT_LOSS, GT_ROWS, TMRError, gt_loss, ptr, require_gpu, size,
                    stream)
-
-
-def _h2d(arr, dev):
-    from .engine import _h2d as h2d
-    return h2d(arr, dev)
+from .graphs import _h2d
 
 
 def _table(dev):

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 from torch import nn
 
-from .engine import conv2d_split
+from .operands import conv2d_split
 
 
 class Decoder_model(nn.Module):

@@ -20,7 +20,8 @@ from torch import nn
 
 from . import host
 from ._lib import PREC_CODES, UNIT_DTYPE, XCORR_ALGOS, TMRError, call, ptr, require_gpu, stream, xcorr
-from .engine import PathConfig, TMREngine, _h2d, _units_to_device
+from .engine import PathConfig, TMREngine
+from .graphs import _h2d, _units_to_device
 
 
 # Host copies of exemplar tensors.  The callers pass the SAME exemplar to

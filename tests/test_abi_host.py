@@ -300,7 +300,7 @@ def test_xcorr_cost_table_committed_crossovers(tmp_path):
     from k=5; 192^2 E=16 fp32 from k=7, one-term at every k); a malformed or incomplete
     table raises instead of silently moving them."""
     import json
-    from tmr_amd import engine as e
+    from tmr_amd import xcorr_cost as e
     assert "xcorr_crossover.json" in e.XCORR_COST_SOURCE
 
     def first_mfma(upi, one):
@@ -318,7 +318,8 @@ def test_xcorr_cost_table_committed_crossovers(tmp_path):
     part.write_text(json.dumps(d))
     with pytest.raises(tmr_amd.TMRError, match="lacks"):
         e._load_xcorr_cost(str(part))
-    assert e._load_xcorr_cost(str(tmp_path / "absent.json")) is None
+    with pytest.raises(tmr_amd.TMRError, match="absent.json"):
+        e._load_xcorr_cost(str(tmp_path / "absent.json"))
 
 
 def test_xcorr_cost_table_matches_kernel_sources():
@@ -330,7 +331,7 @@ def test_xcorr_cost_table_matches_kernel_sources():
     be priced on a kernel that no longer exists."""
     import json
     from tmr_amd import buildinfo
-    from tmr_amd import engine as e
+    from tmr_amd import xcorr_cost as e
     want = buildinfo.source_digest("xcorr")
     cost = json.load(open(e._COST_JSON))
     rec = json.load(open(os.path.join(REPO, "profiles", "xcorr_crossover.json")))
@@ -411,11 +412,11 @@ def test_image_ranges_small_and_vector_forms_agree():
 
 
 def test_clone_outputs_groups_views_of_one_buffer():
-    """engine._clone_outputs (a replayed graph's static outputs copied out):
+    """graphs._clone_outputs (a replayed graph's static outputs copied out):
     contiguous views of one storage (o, b) come back as views of ONE fresh
     copy with the same values; other tensors are cloned; `fp` is kept."""
     import torch
-    from tmr_amd.engine import _clone_outputs
+    from tmr_amd.graphs import _clone_outputs
     ob = torch.arange(50.0)
     o, b = ob[:10].view(2, 1, 5), ob[10:].view(2, 4, 5)
     f = torch.arange(7.0)
@@ -438,7 +439,8 @@ def test_graph_book_bounded_and_failures_remembered():
     LRUs (varied exemplar sizes make a new signature almost every batch);
     a failed capture is remembered, so that signature stays eager without
     re-trying the capture; graphs are an LRU of GRAPH_CACHE."""
-    from tmr_amd.engine import TMREngine, _GraphBook
+    from tmr_amd.engine import TMREngine
+    from tmr_amd.graphs import _GraphBook
     b = _GraphBook(cap=2, seen_cap=4)
     assert not b.want_capture("a") and b.want_capture("a")
     b.put("a", "graph-a")
@@ -468,13 +470,67 @@ def test_heads_image_major_only_for_few_units_per_image():
     """The heads launch runs image-major (an image's units innermost) up to
     HEADS_IMAGE_MAJOR_MAX units per image (config B's 3: faster; config E's
     16: 1.1% slower, profiles/archive/r05/r05t), and only for units in image order."""
-    from tmr_amd import engine
-    upi = engine.TMREngine._units_per_image
-    assert engine.HEADS_IMAGE_MAJOR_MAX == 4
+    from tmr_amd import decoder_plan
+    upi = decoder_plan.units_per_image
+    assert decoder_plan.HEADS_IMAGE_MAJOR_MAX == 4
     assert upi(np.repeat(np.arange(64), 3), 64) == 3
     assert upi(np.repeat(np.arange(8), 16), 8) == 1
     assert upi(np.arange(64), 64) == 1                    # one unit per image
     assert upi(np.array([0, 1, 0, 1, 0, 1]), 2) == 1      # not in image order
+
+
+def test_decoder_plan_routes():
+    """decoder_plan.decoder_plan: the one-layer decoder's route per case, as
+    literals worked out by hand from the flag bits of include/tmr.h
+    (TILED_OUT 1, TILED_INIT 2, INIT_BCAST 4, OUT_BF16 8, INIT_BF16 16,
+    XMAX_PER_UNIT 32, units per image << 8, tile window first << 16 |
+    count << 24).  Most of these routes change speed only, so no value test
+    sees one go missing."""
+    from tmr_amd import _lib as L
+    from tmr_amd.decoder_plan import decoder_plan
+    assert (L.SPLIT_TILED_OUT, L.SPLIT_TILED_INIT, L.SPLIT_INIT_BCAST, L.SPLIT_OUT_BF16, L.SPLIT_INIT_BF16,
+            L.SPLIT_XMAX_PER_UNIT, L.SPLIT_UNITS_PER_IMAGE_SHIFT, L.SPLIT_TILE_FIRST_SHIFT,
+            L.SPLIT_TILE_COUNT_SHIFT) == (1, 2, 4, 8, 16, 32, 8, 16, 24)
+    ordered = lambda B, E: list(np.repeat(np.arange(B), E))  # noqa: E731
+
+    def plan(precision="fp32", fusion=True, E=3, B=2, reuse=False, have_feats=True, unit_image=None, **kw):
+        ui = ordered(B, E) if unit_image is None else unit_image
+        return decoder_plan(tmr_amd.PathConfig(precision=precision, fusion=fusion), True, True, reuse, have_feats,
+                            len(ui), B, ui, **kw)
+
+    def check(p, fold, share, acc16, unscaled, scales, fp_flags, heads_flags, window=(0, 0)):
+        assert (p.fold, p.share, p.acc16, p.unscaled, p.scales) == (fold, share, acc16, unscaled, scales), p
+        w = p.window(4)  # of 4 channel tiles; heads_flags is the word HeadsLaunch.run issues
+        assert (p.fp_flags, p.heads_flags(*w), w) == (fp_flags, heads_flags, window), p
+
+    # E = 3, folded: fp half TILED_OUT|TILED_INIT|INIT_BCAST|XMAX_PER_UNIT, heads TILED_INIT|XMAX_PER_UNIT|3<<8
+    check(plan("fp32"), True, True, False, False, "own", 1 | 2 | 4 | 32, 2 | 32 | 768)
+    # bf16: OUT_BF16 / INIT_BF16 slabs on both launches, no scales
+    check(plan("bf16"), True, True, True, True, "own", 1 | 8 | 2 | 4 | 16, 2 | 16 | 768)
+    check(plan("f16"), True, True, False, False, "own", 39, 802)  # one term, but no bf16 slab
+    # E = 1: unshared, ONE launch from the broadcast bias plane with merged scales; epi 1<<8
+    check(plan(E=1), True, False, False, False, "merged", 0, 2 | 4 | 32 | 256)
+    check(plan(E=1, reuse=True), True, True, False, False, "own", 39, 2 | 32 | 256)  # the module API keeps acc0
+    # no features given: shared but not folded, the fp-half launch has no initial values
+    check(plan(have_feats=False), False, True, False, False, "own", 1 | 32, 802)
+    check(plan(fusion=False), False, False, False, False, "ftm", 0, 32 | 768)  # no src0 at all
+    check(plan(E=5), True, True, False, False, "own", 39, 2 | 32 | 256)  # E > HEADS_IMAGE_MAJOR_MAX
+    check(plan(unit_image=[0, 1, 0, 1, 0, 1]), True, True, False, False, "own", 39, 2 | 32 | 256)  # not image-ordered
+    # box_later: decoder_b's 2 tiles of 4 are left to the points route
+    p = plan(box_later=True, nbt=2)
+    check(p, True, True, False, False, "own", 39,
+          802 | 2 << 16 | 2 << 24, (2, 2))
+    assert p.points_flags() == 2 | 32 | 2 << 24 and p.heads_flags(0, 2) == 802 | 2 << 24  # decoder_b's tiles (0, 2)
+
+
+def test_struct_fields_by_name_only():
+    """_lib._fill (tmr_xcorr_args_t as tmr_gt_loss_args_t): a misspelt field is
+    refused, not turned into a Python attribute beside a zero field."""
+    from tmr_amd import _lib
+    with pytest.raises(_lib.TMRError, match="out_bf_16"):
+        _lib._fill(_lib.XcorrArgs, "tmr_xcorr_args_t", dict(algo=2, out_bf_16=1))
+    a = _lib._fill(_lib.XcorrArgs, "tmr_xcorr_args_t", dict(algo=2, out_bf16=1, relu_out=None))
+    assert (a.algo, a.out_bf16, a.relu_out, a.prec) == (2, 1, None, 0)
 
 
 def test_graph_param_key_follows_the_parameter_dict():

@@ -344,7 +344,7 @@ def test_standalone_template_matching(ttype, poison):
 def test_conv2d_split(prec, poison):
     """conv2d_split at (C 40, N 72, 17 x 33, ks 3) against ATen's fp32 CPU
     conv + LeakyReLU, at test_split_conv_vs_torch's tolerances."""
-    from tmr_amd.engine import conv2d_split
+    from tmr_amd.operands import conv2d_split
     C, N, H, W, ks = 40, 72, 17, 33, 3
     torch.manual_seed(C * 7 + N + ks)
     x = torch.randn(2, C, H, W)

@@ -110,7 +110,7 @@ def test_xcorr_golden(golden):
         units = np.zeros(1, tmr_amd._lib.UNIT_DTYPE)
         units["ht"], units["wt"], units["tmpl_offset"] = h, w, 0
         from tmr_amd._lib import PREC_CODES, XCORR_ALGOS, ptr, stream, xcorr
-        from tmr_amd.engine import _units_to_device
+        from tmr_amd.graphs import _units_to_device
         fd, td = cuda(f), cuda(t.reshape(-1))
         out = torch.empty((1, 1 if sq else C, H, W), device=DEV)
         relu = torch.empty_like(out)
@@ -208,7 +208,7 @@ def test_split_conv_vs_torch(C, N, H, W, ks, leaky, prec):
     CPU) with an acc_init input: "fp32" (3-term fp16 split) within the 1e-5
     contract, one-term bf16 / f16 within their stated tolerances."""
     from tmr_amd._lib import PREC_CODES, call, ptr, stream
-    from tmr_amd.engine import absmax, pack_split_w, pack_split_x
+    from tmr_amd.operands import absmax, pack_split_w, pack_split_x
     torch.manual_seed(C * 7 + N + ks)
     x = torch.randn(2, C, H, W)
     w = torch.randn(N, C, ks, ks) * (1.0 / (ks * C ** 0.5))
@@ -234,7 +234,7 @@ def test_split_conv_scales_and_two_sources(scale):
     rows, and the two-source virtual concat (src0 per image via unit_image,
     src1 per unit) of tmr_split_conv (heads) vs the unsplit fp32 reference."""
     from tmr_amd._lib import call, ptr, stream
-    from tmr_amd.engine import absmax, pack_split_w, pack_split_x
+    from tmr_amd.operands import absmax, pack_split_w, pack_split_x
     torch.manual_seed(3)
     B, U, C0, C1, N, H, W = 2, 3, 24, 40, 136, 18, 35
     x0 = torch.randn(B, C0, H, W) * scale
@@ -302,7 +302,7 @@ def test_xpack_records_bitexact(S, C, H, W, ks):
     kernel otherwise) bit-exact against the torch restatement of the layout,
     padding ring included (the buffer is pre-filled with garbage)."""
     from tmr_amd._lib import PREC_CODES, call, ptr, size, stream
-    from tmr_amd.engine import absmax, absmax_rows, pixel_absmax
+    from tmr_amd.operands import absmax, absmax_rows, pixel_absmax
     torch.manual_seed(11)
     # samples 2^20 apart and a quiet pixel block: the per-sample and per-pixel
     # scale modes (xmax_per_sample 1 / 2) are exercised with real spread
@@ -338,7 +338,7 @@ def test_split_acc_slab_bf16():
     tiled buffer."""
     from tmr_amd._lib import (PREC_CODES, SPLIT_INIT_BF16, SPLIT_OUT_BF16, SPLIT_TILED_INIT,
                               SPLIT_TILED_OUT, call, ptr, size, stream)
-    from tmr_amd.engine import absmax, pack_split_w, pack_split_x
+    from tmr_amd.operands import absmax, pack_split_w, pack_split_x
     torch.manual_seed(5)
     B, U, C0, C1, N, H, W = 2, 3, 40, 48, 136, 19, 37
     x0, x1 = torch.randn(B, C0, H, W), torch.randn(U, C1, H, W)
@@ -1106,7 +1106,7 @@ def test_xcorr_mfma_random_sweep_vs_oracle(seed):
     or one bf16 term (1e-2).  The fused per-unit max and relu output are
     checked bit for bit against the plane.  TMR_XCORR_SWEEP=N for more."""
     from tmr_amd._lib import PREC_CODES, XCORR_ALGOS, call, ptr, size, stream, xcorr
-    from tmr_amd.engine import _h2d, _units_to_device
+    from tmr_amd.graphs import _h2d, _units_to_device
     r = np.random.default_rng(9000 + seed)
     B = int(r.integers(1, 4))
     W = int(r.choice([64, 128, 192, 256]))
@@ -1181,7 +1181,7 @@ def _xcorr_exact(f, t, scale):
 
 def _xcorr_mfma_case(H, W, C, kmax, prec):
     from tmr_amd._lib import PREC_CODES, XCORR_ALGOS, call, ptr, size, stream, xcorr
-    from tmr_amd.engine import _h2d, _units_to_device
+    from tmr_amd.graphs import _h2d, _units_to_device
     B = 2
     f = synth.normal(90 + H + W, (B, C, H, W)) * 1.7
     shapes = [(1, 1), (3, 3), (5, 9), (7, 7), (11, 3), (13, 15), (15, 15), (17, 17), (19, 5), (21, 23),

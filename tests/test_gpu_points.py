@@ -64,7 +64,7 @@ def _operands(d, prec, form, x1=None, ui=UI):
     half over a per-image slab from a store launch of the fp half (bf16 slab
     under "bf16" when slab16); "bcast": both sources in one launch over a
     broadcast plane (the E = 1 path)."""
-    from tmr_amd.engine import absmax, absmax_rows, pack_split_w, pack_split_x, scale_merge
+    from tmr_amd.operands import absmax, absmax_rows, pack_split_w, pack_split_x, scale_merge
     pc = PREC_CODES[prec]
     x1 = d["x1"] if x1 is None else x1
     nu = x1.shape[0]
