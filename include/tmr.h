@@ -390,7 +390,9 @@ int tmr_split_conv(const void *xp0, int C0, const int32_t *unit_image, const voi
  * MFMAs per accumulator element, head arithmetic and tile-order sum -- and
  * writes those four values there; every other element of b is left untouched.
  * tiles (device int32[ntiles][3]): (unit, first candidate, count), count in
- * 1..TMR_POINTS_TILE, a tile within one unit; candidate i of unit u has its
+ * 1..TMR_POINTS_TILE, a tile within one unit, the list in any order (the
+ * launch may process tiles in pairs, entries 2i and 2i+1 in one workgroup,
+ * whatever their units; no value depends on the pairing); candidate i of unit u has its
  * pixel index y*W + x in ((const int32_t *)box)[4 * (u*H*W + i)], where
  * tmr_peaks_decode with TMR_PEAKS_FIND_ONLY leaves it.  acc_init is NULL or
  * tiled (TMR_SPLIT_TILED_INIT, optionally _INIT_BCAST / _INIT_BF16); the

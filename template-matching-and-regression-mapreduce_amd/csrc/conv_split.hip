@@ -842,33 +842,48 @@ int dispatch_ks(int ks, int prec, const SArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- points
-// The same conv + heads at a list of (unit, pixel) points: one block per tile
-// of up to PT points of ONE unit x up to NWAVES 128-channel tiles, wave w
-// owning channel tile NT0 + w (8 n fragments x PT / 16 point columns = the
-// dense wave's 128 accumulator registers).  The MFMA's B operand is the
-// points' gathered records (a record is one K = 32 slice; the records'
-// zero-padded halo makes every 3x3 neighbour a legal address), its A operand
-// the dense kernel's weight records.  The tile's gathered 3x3 records of a
-// half-chunk are staged in LDS once (LDS-DMA, one half-chunk ahead, two
-// buffers) and read by all waves; each wave streams its own weight fragments
-// from L2 into registers one (tap, term) stage ahead of the MFMAs.  (Every
-// wave gathering its own B fragments from L2 -- 64 cache lines per load, 8x
-// redundant -- ran the config-B launch in 15.1 ms.)  Every output element
-// is the dense kernel's chain: acc_init * s_x s_w, then per chunk the hi
-// half-chunk's wh.xh, wl.xh per tap and the lo half-chunk's wh.xl per tap,
-// head_act / head_fma over the tile's channels in the dense lane order, the
-// lane groups as (x0 + x1) + (x2 + x3), the two 64-channel halves, then the
-// tiles in order and the head bias (heads_reduce_kernel).  MFMA columns are
-// independent, so a point's value does not depend on its tile mates.
+// The same conv + heads at a list of (unit, pixel) points.  A block takes TWO
+// host tiles of up to PT points each (tiles 2i and 2i + 1 of the list, which
+// may belong to different units and images; the last block of an odd list
+// takes one) = PP = 128 point columns, x up to 8 128-channel tiles in passes
+// of PTW = 4: wave w owns the 64-channel half w & 1 of channel tile NT0 +
+// 4 pass + (w >> 1) over all 128 columns (NIN = 4 n fragments x PP / 16 = 8
+// column groups = the dense wave's 128 accumulator registers), so a weight
+// fragment is loaded once per 128 points.  A window of more than 4 tiles runs
+// the K loop twice (and gathers B twice).  Everything that belongs to a host
+// tile is per 64-column half: the unit and image, the buffer descriptors of
+// its records, first / count, s_x s_w, the acc_init slab and the stores.
+// The MFMA's B operand is the points' gathered records (a record is one K =
+// 32 slice; the records' zero-padded halo makes every 3x3 neighbour a legal
+// address), its A operand the dense kernel's weight records.  The gathered
+// 3x3 records of a half-chunk are staged in LDS once (LDS-DMA, one half-chunk
+// ahead, two buffers; an instruction covers a third of one host tile's (ky,
+// piece) plane and takes that tile's descriptor) and read by all waves; each
+// wave streams its own weight fragments from L2 into a ring of three register
+// stages, two (tap, term) stages ahead of the MFMAs.  (Every wave gathering its own B fragments
+// from L2 -- 64 cache lines per load, 8x redundant -- ran the config-B launch
+// in 15.1 ms; one 64-point tile per block with a 128-channel tile per wave,
+// each weight fragment loaded once per 64 points, in 7.7 ms.)  Every output
+// element is the dense kernel's chain: acc_init * s_x s_w, then per chunk the
+// hi half-chunk's wh.xh, wl.xh per tap and the lo half-chunk's wh.xl per tap,
+// head_act / head_fma over the half tile's channels in the dense lane order,
+// the lane groups as (x0 + x1) + (x2 + x3), the two 64-channel halves as
+// z[0] + z[1] (the odd wave's through LDS), then the tiles in order and the
+// head bias (heads_reduce_kernel).  MFMA columns are independent, so a
+// point's value does not depend on its tile or block mates.
 constexpr int PT = TMR_POINTS_TILE;
-constexpr int PCG = PT / 16;  // 16-point column groups
-static_assert(PT == 64 && 4 * PT <= NTHREADS, "points tile: one gather lane per point");
+constexpr int PP = 2 * PT;         // point columns per block
+constexpr int PCG = PP / 16;       // 16-point column groups per block (PCG / 2 per host tile)
+constexpr int PTW = NWAVES / WNS;  // channel tiles per pass
+static_assert(PT == 64 && 4 * PP == NTHREADS, "points block: one store lane per head and point");
+static_assert(WNS == 2 && NWAVES == 2 * P, "points block: a wave per 64-channel half; gathers dealt by (piece, half)");
 
 struct PArgs {
     SArgs s;
     const float *head_bias;
     const float *box;       // the finder's rows: pixel index in ((int *)box)[4 * (u * HW + i)]
     const int32_t *tiles;   // [ntiles][3]: unit, first candidate, count (1..PT)
+    int ntiles;
     float *b;               // [U][4][H][W], written at the points only
 };
 
@@ -877,113 +892,152 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     typedef Prec<PREC> PR;
     typedef typename PR::V V;
     constexpr int T = KS * KS, HALVES = PR::HALVES, WREC = PR::WREC;
-    constexpr int NF = BM / 16;                       // n fragments per tile
+    constexpr int NF = NIN;                           // n fragments per wave: a 64-channel half tile
     constexpr int NS = HALVES == 2 ? 3 * T : T;       // (tap, term) stages per chunk
     const SArgs &a = pa.s;
-    // LDS: the tile's gathered B records of one half-chunk, [tap][piece][point]
-    // 16-B slots (the dense halo's piece planes: a fragment read takes 16
-    // consecutive slots of one plane), two buffers; then the tiles' head sums
-    constexpr int BB = T * P * PT * 16;  // bytes per B buffer
+    // LDS: the block's gathered B records of one half-chunk, [ky][piece][point]
+    // [kx] 16-B slots (a point's kx = 0..2 pieces of a tap row are 48
+    // contiguous bytes of the packed plane and of the image; a fragment read
+    // takes the slots of 16 consecutive points at one kx), two buffers; then
+    // the tiles' head sums.
+    // Between the K loops the second buffer's head holds the odd waves' sums.
+    constexpr int BB = T * P * PP * 16;  // bytes per B buffer
     extern __shared__ __attribute__((aligned(16))) char plds[];
     char *Bs = plds;
-    float(*red)[4][PT] = reinterpret_cast<float(*)[4][PT]>(plds + 2 * BB);
+    float(*red)[4][PP] = reinterpret_cast<float(*)[4][PP]>(plds + 2 * BB);
+    float(*xch)[4][PP] = reinterpret_cast<float(*)[4][PP]>(plds + BB);
+    static_assert(PTW * 4 * PP * sizeof(float) <= BB, "the odd waves' sums fit a B buffer");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wh = wave & 1, wt = wave >> 1;  // this wave's 64-channel half and its tile of a pass
     const int l16 = lane & 15, kg = lane >> 4;
     const int HW = a.H * a.W;
-    const int32_t *tl = pa.tiles + 3 * (size_t)blockIdx.x;
-    const int u = min(max(tl[0], 0), a.U - 1);
-    const int first = min(max(tl[1], 0), HW - 1), cnt = min(max(tl[2], 0), PT);
-    const int img = a.unit_image ? a.unit_image[u] : u;
+    // the block's two host tiles (column half hh = tile 2 * block + hh); a
+    // half past the list repeats the block's first tile with no point to store
+    int tu[2], tfirst[2], tcnt[2], timg[2];
+    float sxw[2];
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        const int64_t ti = 2 * (int64_t)blockIdx.x + hh;
+        const bool have = ti < pa.ntiles;
+        const int32_t *tl = pa.tiles + 3 * (have ? ti : ti - hh);
+        tu[hh] = min(max(tl[0], 0), a.U - 1);
+        tfirst[hh] = min(max(tl[1], 0), HW - 1);
+        tcnt[hh] = have ? min(max(tl[2], 0), PT) : 0;
+        timg[hh] = a.unit_image ? a.unit_image[tu[hh]] : tu[hh];
+        sxw[hh] = split_sxw<PREC>(a, tu[hh]);
+    }
     const int NC = a.NC0 + a.NC1;
-    // a wave past the window's tiles repeats its first tile (it shares the
-    // gathers and the barriers) and stores nothing
-    const bool active = wave < a.NTW;
-    const int nt = a.NT0 + (active ? wave : 0);
-    const int *pixi = reinterpret_cast<const int *>(pa.box) + 4 * (size_t)u * HW;
-    // point p's pixel (a point past the tile's count repeats a legal candidate
-    // row and is never stored; a pixel index is clamped into the map, so no
-    // gather leaves the padded plane)
-    auto pixel = [&](int p) { return min(max(pixi[4 * (size_t)min(first + (p < cnt ? p : 0), HW - 1)], 0), HW - 1); };
+    // point p of a host tile: its pixel (a point past the tile's count repeats
+    // a legal candidate row and is never stored; a pixel index is clamped into
+    // the map, so no gather leaves the padded plane)
+    auto pixel = [&](int u, int first, int cnt, int p) {
+        const int *pixi = reinterpret_cast<const int *>(pa.box) + 4 * (size_t)u * HW;
+        return min(max(pixi[4 * (size_t)min(first + (p < cnt ? p : 0), HW - 1)], 0), HW - 1);
+    };
+    // the host tile this wave gathers for and stores: column half wh
+    const int gu = wh ? tu[1] : tu[0], gfirst = wh ? tfirst[1] : tfirst[0], gcnt = wh ? tcnt[1] : tcnt[0];
+    const int gimg = wh ? timg[1] : timg[0];
 
-    {
-        // this lane's point of each column group
-        int py[PCG], px[PCG];
+    // operands through buffer descriptors (SGPRs): every load is base +
+    // uniform soffset + a 32-bit per-lane voffset (+ an immediate), so the
+    // loop holds two address registers per lane, and the range check
+    // turns a stray read into zeros instead of a fault
+    const uint32_t cstride = (uint32_t)a.Hp * a.Wp * XREC;
+    const int h0 = a.NC0 * HALVES, h1 = a.NC1 * HALVES;
+    const __amdgpu_buffer_rsrc_t xr0 = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)(h0 ? a.x0 + (size_t)gimg * h0 * cstride : a.x1), (short)0, h0 * cstride, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr1 = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)(h1 ? a.x1 + (size_t)gu * h1 * cstride : a.x0), (short)0, h1 * cstride, 0x00020000);
+    const uint32_t tapstride = (uint32_t)NC * a.Npad * WREC;
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)a.wp, (short)0, T * tapstride, 0x00020000);
+    // The gather of half-chunk hc into buffer hc & 1 by LDS-DMA: the KS wave
+    // instructions of (ky, piece, half) fill the half's PT * KS slots of that
+    // plane in image order, lane l of instruction i = slot 64 i + l = (point,
+    // kx), through the half's descriptor: three neighbouring lanes read 48
+    // contiguous bytes, so an instruction touches a third of the cache lines
+    // of a lane-per-point gather (6.7-6.8 -> 6.1 ms at config B).
+    // Wave w issues piece w >> 1 of half w & 1 for every ky.  Issued at the
+    // start of half-chunk hc - 1 (the buffer was last read in hc - 2, before
+    // the barrier that ended it) and complete before the barrier that ends
+    // hc - 1.  The gather is what the launch waits for (config B, same box:
+    // 6.35 ms; 5.0 ms with the second K loop's gathers left out, 3.95 ms with
+    // none, 4.3 ms with every lane reading one pixel): the candidates touch
+    // most 128-B lines of the packed planes for 48 B each, once per K loop.
+    // Measured and dropped: a wave's gather instructions spread over the
+    // half-chunk's stages (7.7 ms: vmcnt counts in issue order, so every
+    // stage's wait for its weights then waits for a gather instruction), and
+    // waves 4-7 alone gathering, so that a stalled wave's SIMD partner keeps
+    // the matrix pipe (6.3 ms: no change).
+    uint32_t goff[KS];
 #pragma unroll
-        for (int j = 0; j < PCG; ++j) {
-            const int pix = pixel(j * 16 + l16);
-            py[j] = pix / a.W;
-            px[j] = pix - py[j] * a.W;
-        }
-        // operands through buffer descriptors (SGPRs): every load is base +
-        // uniform soffset + a 32-bit per-lane voffset (+ an immediate), so the
-        // loop holds two address registers per lane, and the range check
-        // turns a stray read into zeros instead of a fault
-        const uint32_t cstride = (uint32_t)a.Hp * a.Wp * XREC;
-        const int h0 = a.NC0 * HALVES, h1 = a.NC1 * HALVES;
-        const __amdgpu_buffer_rsrc_t xr0 = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(h0 ? a.x0 + (size_t)img * h0 * cstride : a.x1), (short)0, h0 * cstride, 0x00020000);
-        const __amdgpu_buffer_rsrc_t xr1 = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(h1 ? a.x1 + (size_t)u * h1 * cstride : a.x0), (short)0, h1 * cstride, 0x00020000);
-        const uint32_t tapstride = (uint32_t)NC * a.Npad * WREC;
-        const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)a.wp, (short)0, T * tapstride, 0x00020000);
-        const uint32_t aoff = (uint32_t)kg * a.Npad * 16 + ((uint32_t)nt * BM + l16) * 16;
-        // The gather of half-chunk hc into buffer hc & 1 by LDS-DMA: wave
-        // instruction i = tap * 4 + piece fills that plane's PT slots, lane =
-        // point (its record's piece: 16 B), the instructions dealt round robin
-        // to the waves.  Issued at the start of half-chunk hc - 1 (the buffer
-        // was last read in hc - 2, before the barrier that ended it) and
-        // complete before the barrier that ends hc - 1.
-        uint32_t goff;
-        {
-            const int pix = pixel(lane), y = pix / a.W;
-            goff = (uint32_t)(y * a.Wp + (pix - y * a.W)) * 16;
-        }
-        const uint32_t qstride = (uint32_t)a.Hp * a.Wp * 16;
-        auto gather = [&](int hc) {
-            const bool s0 = hc < h0;
-            const uint32_t hs_ = (uint32_t)(s0 ? hc : hc - h0) * cstride;
+    for (int i = 0; i < KS; ++i) {
+        const int g = 64 * i + lane;
+        const int pix = pixel(gu, gfirst, gcnt, g / KS), y = pix / a.W;
+        goff[i] = (uint32_t)(y * a.Wp + (pix - y * a.W) + g % KS) * 16;
+    }
+    const uint32_t qstride = (uint32_t)a.Hp * a.Wp * 16;
+    auto gather = [&](int hc) {
+        const bool s0 = hc < h0;
+        const uint32_t hs_ = (uint32_t)(s0 ? hc : hc - h0) * cstride + wt * qstride;
 #pragma unroll
-            for (int m = 0; m < (T * P + NWAVES - 1) / NWAVES; ++m) {
-                const int i = wave + NWAVES * m;
-                if (i < T * P) {
-                    const int tap = i / P, q = i % P, ky = tap / KS, kx = tap % KS;
-                    buffer_lds16(s0 ? xr0 : xr1, (lds_ptr_t)(Bs + (hc & 1) * BB + i * (PT * 16)), goff,
-                                 hs_ + q * qstride + (uint32_t)(ky * a.Wp + kx) * 16);
-                }
-            }
-        };
-        const int bfo = kg * (PT * 16) + l16 * 16;  // this lane's slot of a (tap, column group 0) fragment
-        auto bfrag = [&](int hc, int tap, int j) -> V {
-            return *reinterpret_cast<const V *>(Bs + (hc & 1) * BB + tap * (P * PT * 16) + bfo + j * 256);
-        };
+        for (int ky = 0; ky < KS; ++ky)
+#pragma unroll
+            for (int i = 0; i < KS; ++i)
+                buffer_lds16(s0 ? xr0 : xr1,
+                             (lds_ptr_t)(Bs + (hc & 1) * BB + (((ky * P + wt) * PP + wh * PT) * KS + 64 * i) * 16), goff[i],
+                             hs_ + (uint32_t)(ky * a.Wp) * 16);
+    };
+    // this lane's slot of a (ky, kx = 0, column group 0) fragment: a point's
+    // slots are KS * 16 B apart, 12 banks: the 16 lanes of a ds_read_b128
+    // group start on 16 different multiples of 4 banks
+    const int bfo = kg * (PP * KS * 16) + l16 * (KS * 16);
+    auto bfrag = [&](int hc, int tap, int j) -> V {
+        return *reinterpret_cast<const V *>(Bs + (hc & 1) * BB + (tap / KS) * (P * PP * KS * 16) + bfo +
+                                            j * (16 * KS * 16) + (tap % KS) * 16);
+    };
+
+    const int npass = a.NTW > PTW ? 2 : 1;
+    for (int pass = 0; pass < npass; ++pass) {
+        // a wave past the window's tiles repeats the window's first tile (it
+        // shares the gathers and the barriers) and stores nothing
+        const int wtile = pass * PTW + wt;
+        const bool active = wtile < a.NTW;
+        const int nt = a.NT0 + (active ? wtile : 0);
+        const uint32_t aoff = (uint32_t)kg * a.Npad * 16 + ((uint32_t)nt * BM + wh * (BM / 2) + l16) * 16;
+        // (pass 1: buffer 0 was last read before the K loop's closing barrier;
+        // the odd waves' sums of pass 0 sit in buffer 1)
         gather(0);
 
-        const float sxw = split_sxw<PREC>(a, u);
         f32x4 acc[NF][PCG];
         if (a.acc_init) {  // tiled (host-checked): the dense kernel's element of slab / tile / wave / lane
-            const int islab = (a.flags & TMR_SPLIT_INIT_BCAST) ? 0 : img;
             const bool i16 = a.flags & TMR_SPLIT_INIT_BF16;
 #pragma unroll
             for (int j = 0; j < PCG; ++j) {
-                const int mt = (py[j] / TH) * a.TXN + px[j] / TW;
-                const int wpix = (py[j] % TH) >> 2, jp = ((py[j] & 3) << 1) | ((px[j] % TW) >> 4);
-                // 16-B group index of (wave wpix * WNS, in 0): + (f / NIN) waves, + (f % NIN) * 8 groups of 64
-                const size_t g4 = (((((size_t)islab * a.NT + nt) * a.MT + mt) * NWAVES + wpix * WNS) * ACCW) / 4 +
-                                  jp * 64 + kg * 16 + (px[j] & 15);
+                constexpr int HJ = PCG / 2;  // column groups per host tile
+                const int hh = j / HJ;
+                const int pix = pixel(tu[hh], tfirst[hh], tcnt[hh], (j % HJ) * 16 + l16);
+                const int py = pix / a.W, px = pix - py * a.W;
+                const float sx = sxw[hh];
+                const int islab = (a.flags & TMR_SPLIT_INIT_BCAST) ? 0 : timg[hh];
+                const int mt = (py / TH) * a.TXN + px / TW;
+                const int wpix = (py % TH) >> 2, jp = ((py & 3) << 1) | ((px % TW) >> 4);
+                // 16-B group index of (wave wpix * WNS + wh, in 0): + f * 8 groups of 64
+                const size_t g4 = (((((size_t)islab * a.NT + nt) * a.MT + mt) * NWAVES + wpix * WNS + wh) * ACCW) / 4 +
+                                  jp * 64 + kg * 16 + (px & 15);
                 if (i16) {
                     const b4 *ai = reinterpret_cast<const b4 *>(a.acc_init) + g4;
 #pragma unroll
                     for (int f = 0; f < NF; ++f)
-                        acc[f][j] = __builtin_convertvector(ai[(f / NIN) * (ACCW / 4) + (f % NIN) * 8 * 64], f32x4) * sxw;
+                        acc[f][j] = __builtin_convertvector(ai[f * 8 * 64], f32x4) * sx;
                 } else {
                     const f32x4 *ai = reinterpret_cast<const f32x4 *>(a.acc_init) + g4;
 #pragma unroll
                     for (int f = 0; f < NF; ++f)
-                        acc[f][j] = ai[(f / NIN) * (ACCW / 4) + (f % NIN) * 8 * 64] * sxw;
+                        acc[f][j] = ai[f * 8 * 64] * sx;
                 }
             }
         } else {
@@ -1001,19 +1055,24 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         auto st_newb = [](int s) { return !(HALVES == 2 && s < 2 * T && (s & 1)); };
         auto st_first = [](int s) { return s == 0 || (HALVES == 2 && s == 2 * T); };  // of a half-chunk
         auto st_last = [](int s) { return s == NS - 1 || (HALVES == 2 && s == 2 * T - 1); };
-        V an[NF], bn[PCG];  // the next stage's fragments
-        auto load_stage = [&](int c, int s) {
-            const int tap = st_tap(s);
-            const uint32_t as = (uint32_t)tap * tapstride + (uint32_t)c * a.Npad * WREC +
+        // weight fragments: a ring of AR stages, stage s in slot s % AR, loaded
+        // AR - 1 stages ahead (NS is a multiple of AR, so the slots run on
+        // from chunk to chunk)
+        constexpr int AR = 3;
+        static_assert(NS % AR == 0 && NS >= AR, "weight ring");
+        V ar[AR][NF];
+        auto load_stage = [&](int c, int s) {  // (past the end: a harmless re-read of the last chunk)
+            if (s >= NS) {
+                s -= NS;
+                c = c + 1 < NC ? c + 1 : c;
+            }
+            const uint32_t as = (uint32_t)st_tap(s) * tapstride + (uint32_t)c * a.Npad * WREC +
                                 (uint32_t)st_term(s) * 4 * a.Npad * 16;
 #pragma unroll
-            for (int f = 0; f < NF; ++f) an[f] = buffer_load16<V>(wr, aoff + f * 256, as);
-            if (st_newb(s) && !st_first(s)) {  // (a half-chunk's first B waits for its barrier)
-#pragma unroll
-                for (int j = 0; j < PCG; ++j) bn[j] = bfrag(c * HALVES + st_part(s), tap, j);
-            }
+            for (int f = 0; f < NF; ++f) ar[s % AR][f] = buffer_load16<V>(wr, aoff + f * 256, as);
         };
-        load_stage(0, 0);
+#pragma unroll
+        for (int s = 0; s < AR - 1; ++s) load_stage(0, s);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         V bc[PCG];
@@ -1022,53 +1081,58 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int hc = c * HALVES + st_part(s);
-                V ac[NF];
-#pragma unroll
-                for (int f = 0; f < NF; ++f) ac[f] = an[f];
+                // the loads of stage s + AR - 1 stay ahead of this stage's MFMAs
+                // and behind the last stage's (unpinned, the scheduler hoists
+                // whole chunks of loads and spills the accumulators); at a
+                // half-chunk's first stage they go ahead of the next gather, so
+                // that no stage's wait for its weights (vmcnt counts in issue
+                // order) covers a gather issued less than AR - 1 stages before
+                load_stage(c, s + AR - 1);
                 if (st_first(s)) {
                     if (hc + 1 < NHC) gather(hc + 1);
 #pragma unroll
                     for (int j = 0; j < PCG; ++j) bc[j] = bfrag(hc, st_tap(s), j);
-                } else if (st_newb(s)) {
-#pragma unroll
-                    for (int j = 0; j < PCG; ++j) bc[j] = bn[j];
                 }
-                // the next stage (past the end: a harmless re-read of the last chunk's first)
-                if (s + 1 < NS)
-                    load_stage(c, s + 1);
-                else
-                    load_stage(c + 1 < NC ? c + 1 : c, 0);
-                // the loads stay ahead of this stage's MFMAs and behind the last
-                // stage's (unpinned, the scheduler hoists whole chunks of loads
-                // and spills the accumulators)
+                // A column group's B fragment is dead after its NF MFMAs: the
+                // next stage's, where that stage takes a new tap of the same
+                // half-chunk, is read into its place (a half-chunk's first B
+                // waits for its barrier, above)
+                const bool nextb = s + 1 < NS && st_newb(s + 1) && !st_first(s + 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < PCG; ++j)
+                for (int j = 0; j < PCG; ++j) {
 #pragma unroll
-                    for (int f = 0; f < NF; ++f) acc[f][j] = mma(ac[f], bc[j], acc[f][j]);
+                    for (int f = 0; f < NF; ++f) acc[f][j] = mma(ar[s % AR][f], bc[j], acc[f][j]);
+                    if (nextb) {
+                        bc[j] = bfrag(hc, st_tap(s + 1), j);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
                 __builtin_amdgcn_sched_barrier(0);
-                if (st_last(s)) {  // the next half-chunk's gather has landed; this one's buffer is free
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (st_last(s)) {
+                    // the next half-chunk's gather has landed (it is older than
+                    // the (AR - 1) NF weight loads that may stay in flight: a
+                    // half-chunk has more than AR - 1 stages); this one's buffer
+                    // is free
+                    static_assert((AR - 1) * NF == 8 && T > AR - 1, "the counted wait below");
+                    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
                     __syncthreads();
                 }
             }
         }
 
-        // heads of this tile: lane group kg holds rows n = 16 f + 4 kg + r
-        const float inv = 1.0f / sxw;
-        const f2 inv2 = {inv, inv};
-        f2 hs[WNS][PCG / 2][NHEAD];
+        // heads of this half tile: lane group kg holds rows n = 64 wh + 16 f +
+        // 4 kg + r; column groups (2q, 2q + 1) lie in one host tile
+        f2 hs[PCG / 2][NHEAD];
 #pragma unroll
-        for (int w = 0; w < WNS; ++w)
+        for (int q = 0; q < PCG / 2; ++q)
 #pragma unroll
-            for (int q = 0; q < PCG / 2; ++q)
-#pragma unroll
-                for (int k = 0; k < NHEAD; ++k) hs[w][q][k] = (f2){0.0f, 0.0f};
+            for (int k = 0; k < NHEAD; ++k) hs[q][k] = (f2){0.0f, 0.0f};
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int n = nt * BM + f * 16 + 4 * kg + r;
+                const int n = nt * BM + wh * (BM / 2) + f * 16 + 4 * kg + r;
                 const float bv = n < a.N ? a.bias[n] : 0.0f;
                 const f2 bn2 = {bv, bv};
                 f2 hw2[NHEAD];
@@ -1078,45 +1142,68 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
                     hw2[k] = (f2){h, h};
                 }
 #pragma unroll
-                for (int q = 0; q < PCG / 2; ++q)
-                    head_fma(head_act((f2){acc[f][2 * q][r], acc[f][2 * q + 1][r]}, inv2, bn2, a.leaky), hw2,
-                             hs[f / NIN][q]);
+                for (int q = 0; q < PCG / 2; ++q) {
+                    const float inv = 1.0f / sxw[q / (PCG / 4)];
+                    head_fma(head_act((f2){acc[f][2 * q][r], acc[f][2 * q + 1][r]}, (f2){inv, inv}, bn2, a.leaky), hw2,
+                             hs[q]);
+                }
             }
-        // over the lane groups, (x0 + x1) + (x2 + x3), then the two halves
+        // over the lane groups, (x0 + x1) + (x2 + x3)
+        float z[PCG / 2][4][2];
 #pragma unroll
         for (int q = 0; q < PCG / 2; ++q)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    float z[WNS];
-#pragma unroll
-                    for (int w = 0; w < WNS; ++w) {
-                        const float x = hs[w][q][k][e];
-                        const float y = x + __shfl_xor(x, 16);
-                        z[w] = y + __shfl_xor(y, 32);
-                    }
-                    if (kg == 0 && active) red[wave][k][(2 * q + e) * 16 + l16] = WNS == 2 ? z[0] + z[1] : z[0];
+                    const float x = hs[q][k][e];
+                    const float y = x + __shfl_xor(x, 16);
+                    z[q][k][e] = y + __shfl_xor(y, 32);
                 }
+        // then the two halves, z[0] + z[1]: the odd wave's through LDS (the
+        // K loop's closing barrier freed the B buffers; buffer 1 is next
+        // written by the gather a pass issues after its opening barrier)
+        if (wh == 1 && kg == 0 && active) {
+#pragma unroll
+            for (int q = 0; q < PCG / 2; ++q)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) xch[wt][k][(2 * q + e) * 16 + l16] = z[q][k][e];
+        }
+        __syncthreads();
+        if (wh == 0 && kg == 0 && active) {
+#pragma unroll
+            for (int q = 0; q < PCG / 2; ++q)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int p = (2 * q + e) * 16 + l16;
+                        red[wtile][k][p] = z[q][k][e] + xch[wt][k][p];
+                    }
+        }
     }
     __syncthreads();
-    if (tid < 4 * PT) {
-        const int k = tid / PT, p = tid % PT;
-        if (p < cnt) {
-            const int pix = pixel(p);
+    {
+        // thread (head k, column p): wave w stores for the host tile of half w & 1
+        const int k = tid / PP, p = tid % PP, pl = p % PT;
+        if (pl < gcnt) {
+            const int pix = pixel(gu, gfirst, gcnt, pl);
             float s = 0.0f;
             for (int t = 0; t < a.NTW; ++t) s += red[t][k][p];
-            pa.b[((size_t)u * 4 + k) * HW + pix] = s + pa.head_bias[k];
+            pa.b[((size_t)gu * 4 + k) * HW + pix] = s + pa.head_bias[k];
         }
     }
 }
 
 template <int PREC>
 int launch_points(const PArgs &pa, int ntiles, hipStream_t s) {
-    constexpr size_t lds = 2 * 9 * P * PT * 16 + NWAVES * 4 * PT * sizeof(float);
+    constexpr size_t lds = 2 * 9 * P * PP * 16 + NWAVES * 4 * PP * sizeof(float);
+    static_assert(lds <= LDS_KB * 1024, "LDS");
     auto kern = split_points_kernel<3, PREC>;
     if (tmr_set_max_lds((const void *)kern, lds) != hipSuccess) return TMR_E_HIP;
-    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(NTHREADS), lds, s, pa);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((ntiles + 1) / 2)), dim3(NTHREADS), lds, s, pa);
     TMR_CHECK_LAUNCH();
     return TMR_OK;
 }
@@ -1713,10 +1800,11 @@ extern "C" int tmr_split_conv_points(const void *xp0, int C0, const int32_t *uni
     a.flags = flags & 0xff;
     a.EI = 1;
     TMR_REQUIRE(tile_window(flags, a.NT, a.NT0, a.NTW));
-    if (ks != 3 || a.NTW > NWAVES) return TMR_E_UNSUPPORTED;
+    if (ks != 3 || a.NTW > 2 * PTW) return TMR_E_UNSUPPORTED;
     pa.head_bias = head_bias;
     pa.box = box;
     pa.tiles = tiles;
+    pa.ntiles = ntiles;
     pa.b = b;
     if (ntiles == 0) return TMR_OK;
     hipStream_t s = tmr_stream(stream);

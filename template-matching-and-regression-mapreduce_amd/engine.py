@@ -514,8 +514,9 @@ class TMREngine:
     # when the candidates exceed BOX_POINTS_CROSSOVER of the pixels.
     box_at_peaks = "auto"  # "auto" | "always" | "never"
     # (dense decoder_b tiles' time per pixel) / (points launch's time per point), measured on one
-    # box at configs B-E (profiles/r07points/crossover.json): 3-term fp16 0.40-0.43, one term 0.29
-    BOX_POINTS_CROSSOVER = {"fp32": 0.40, "bf16": 0.28, "f16": 0.28}
+    # box at configs B-E (profiles/r08points/crossover.json, profiles/points_crossover.py): 3-term fp16
+    # 0.50-0.56, one term 0.48
+    BOX_POINTS_CROSSOVER = {"fp32": 0.50, "bf16": 0.47, "f16": 0.47}
 
     def _box_tiles(self) -> int:
         """decoder_b's 128-channel tiles at the front of decoder_b || decoder_o."""
