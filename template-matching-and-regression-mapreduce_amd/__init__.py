@@ -17,6 +17,7 @@ from .criterion import SetCriterion_TM, WeightedFocalLoss, build_criterion, gIoU
 from .tm_utils import (NMS, GT_map, Get_pred_boxes, Make_Template_size_predictions,  # noqa: F401
                        NMS_process, adaptive_kernel_generater, calc_area, custom_shape_3x3_maxpool2d,
                        map_normalization)
+from .refine import SAM_box_refiner, mask_boxes  # noqa: F401
 
 __all__ = [
     "TemplateMatching", "Decoder_model", "ObjectnessHead", "BboxesHead", "matching_net",
@@ -24,5 +25,6 @@ __all__ = [
     "adaptive_kernel_generater", "Make_Template_size_predictions", "custom_shape_3x3_maxpool2d",
     "calc_area", "map_normalization", "TMREngine", "PathConfig",
     "GT_map", "SetCriterion_TM", "build_criterion", "gIoU_loss", "WeightedFocalLoss",
+    "SAM_box_refiner", "mask_boxes",
     "TMRError", "build_backbone", "register_backbone", "unregister_backbone", "FeatureInput",
 ]

@@ -129,6 +129,23 @@ SIGNATURES = {
 }
 
 
+class MaskBoxesArgs(ctypes.Structure):
+    """tmr_mask_boxes_args_t (include/tmr_refine.h)."""
+    _fields_ = [("masks", _P), ("logits", _P), ("iou", _P), ("scaler", _P), ("boxes", _P), ("refs", _P),
+                ("logits_out", _P), ("work", _P), ("N", _L), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("mode", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+# the optional evaluation extension (include/tmr_refine.h): exported by the same libtmr.so, outside
+# the core ABI above
+EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_refine.h")
+EXT_SIGNATURES = {
+    "tmr_mask_boxes": (_I, [ctypes.POINTER(MaskBoxesArgs), _P]),
+}
+REFINE_FORWARD, REFINE_SCALED = 0, 1  # tmr_mask_boxes_args_t.mode
+MASK_BOXES_WORK_PER_MASK = 16  # TMR_MASK_BOXES_WORK_BYTES(N) = 16 * N
+
+
 class TMRError(RuntimeError):
     pass
 
@@ -146,7 +163,7 @@ def load() -> ctypes.CDLL:
                 f"libtmr.so not found at {LIB_PATH}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -228,6 +245,12 @@ def gt_loss_args(**fields) -> GtLossArgs:
 def gt_loss(stream_=None, **fields) -> None:
     """tmr_gt_loss(&args, stream)."""
     check(load().tmr_gt_loss(ctypes.byref(gt_loss_args(**fields)), stream_), "tmr_gt_loss")
+
+
+def mask_boxes(stream_=None, **fields) -> None:
+    """tmr_mask_boxes(&args, stream) (include/tmr_refine.h)."""
+    check(load().tmr_mask_boxes(ctypes.byref(_fill(MaskBoxesArgs, "tmr_mask_boxes_args_t", fields)), stream_),
+          "tmr_mask_boxes")
 
 
 def require_gpu(t: torch.Tensor, name: str = "input") -> None:

@@ -911,13 +911,50 @@ class TMREngine:
              ptr(out_l), ptr(out_b), ptr(out_r), None, ptr(kept), stream())
         return logits, box, ref, counts, torch.cat([counts, kept]), out_l, out_b, out_r
 
+    def _detect_refined(self, feats, unit_image, boxes, params, shape, iou_threshold, refiner, image,
+                        sam_features, refine_exemplars):
+        """detect() with a box refiner: the eager route up to the candidates
+        (no speculative NMS), the per-image lists in exemplar order (an empty
+        unit contributes its dummy row, as Get_pred_boxes), the refiner, then
+        the package's NMS."""
+        from .tm_utils import NMS
+
+        if image is None or sam_features is None:
+            raise TMRError("detect(refiner=...) needs image and sam_features")
+        B, E, cap = shape
+        self.last_graph, self.last_nms_small = "eager", False
+        if self.box_at_peaks_ok():
+            logits, box, ref, _, counts_host = self._detect_box_at_peaks(feats, unit_image, boxes, params)
+        else:
+            self.last_box_route = None
+            logits, box, ref, counts = self._forward_peaks(feats, unit_image, boxes, params)
+            counts_host = counts.cpu().numpy()  # torch.where-style sync (TM_utils.py:254)
+        rows = np.maximum(counts_host, 1)  # (row 0 of an empty unit holds the dummy row)
+        L, Bx, R = [], [], []
+        for i in range(B):
+            us = range(i * E, (i + 1) * E)
+            L.append(torch.cat([logits[u * cap:u * cap + int(rows[u])] for u in us]))
+            Bx.append(torch.cat([box[u * cap:u * cap + int(rows[u])] for u in us]))
+            R.append(torch.cat([ref[u * cap:u * cap + int(rows[u])] for u in us]))
+        if refine_exemplars is not None:
+            L, Bx, R = refiner.forward_refine(L, Bx, R, image, refine_exemplars, sam_features)
+        else:
+            L, Bx, R = refiner(L, Bx, R, image, sam_features)
+        return NMS(L, Bx, R, iou_threshold)
+
     def detect(self, feats: torch.Tensor, exemplars, cls_ths: float, iou_threshold: float,
-               ablation_b: bool = False, ablation_c: bool = False):
+               ablation_b: bool = False, ablation_c: bool = False, refiner=None, image=None,
+               sam_features=None, refine_exemplars=None):
         """The reference's multi-exemplar inference (demo.py:106-130,
         trainer.py:95-118) for a batch: per image, one forward per exemplar,
         Get_pred_boxes, concat in exemplar order, one NMS.
 
         exemplars: [B,E,4] normalised xyxy (array or tensor).
+        refiner (a SAM_box_refiner): the --refine_box order of
+        trainer.py:106-118: the candidates of every exemplar, concatenated
+        per image, go through refiner.forward(.., image, sam_features) (or
+        forward_refine with refine_exemplars) before the NMS; image [B,3,h,w]
+        and sam_features (per image [C,he,we]) are the refiner's inputs.
         Returns per-image lists (logits [k,2], boxes [k,4], refs [k,2])."""
         ex = exemplars.detach().cpu().numpy() if isinstance(exemplars, torch.Tensor) else \
             np.asarray(exemplars)
@@ -933,6 +970,9 @@ class TMREngine:
         U = B * E
         unit_off = np.arange(U, dtype=np.int64) * (H * W)
         seg = np.arange(0, U + 1, E, dtype=np.int64)
+        if refiner is not None:
+            return self._detect_refined(feats, unit_image, boxes, params, (B, E, H * W), iou_threshold, refiner,
+                                        image, sam_features, refine_exemplars)
         if not (self.use_graphs and U <= self.GRAPH_MAX_UNITS):
             # the unspeculated eager route (no graph prep at all): the
             # regression only at the peaks where that applies

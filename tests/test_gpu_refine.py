@@ -1,0 +1,427 @@
+"""GPU: the SAM box refiner (tmr_mask_boxes, tmr_amd.mask_boxes,
+tmr_amd.SAM_box_refiner, TMREngine.detect(refiner=...)).
+
+* the module, fed the recorded per-call outputs of the two SAM stand-ins of
+  tests/golden/refine.npz, reproduces the reference refiner's lists exactly
+  (forward and forward_refine), and hands the stand-ins the recorded boxes;
+* mask_boxes equals the numpy restatement of include/tmr_refine.h
+  (tests/refine_ref.py) exactly: the rule is stated operation by operation,
+  so no tolerance applies;
+* at the workload's own size (50 masks 256^2 -> 1024^2) it equals
+  F.interpolate + threshold + min / max in plain torch on the same device;
+  the masks are drawn so that no box depends on the last bits of the
+  interpolated values (eps = 1e-5 * max|mask| on either side of zero);
+* the whole route under the guard-banded, poisoning allocator;
+* detect(refiner=...) equals Get_pred_boxes -> refiner -> NMS.
+
+An equality is exact with a NaN equal to a NaN (0 * inf has another sign bit
+on the GPU than on the CPU that made the fixture).
+"""
+import numpy as np
+import pytest
+import torch
+from torch.nn import functional as F
+
+import guarded_alloc as ga
+import oracle
+import refine_ref
+import tmr_amd
+from tmr_amd import synth
+from test_refine_host import chunks, same
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+f32 = np.float32
+
+
+def cuda(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+# ------------------------------------------------------------------ replay stand-ins
+class PromptReplay:
+    """The prompt encoder of the fixture: checks the boxes of every call."""
+
+    def __init__(self, g, tag, place=cuda):
+        self.g, self.tag, self.k, self.place = g, tag, 0, place
+        self.emb = tuple(int(v) for v in g["emb_size"])
+
+    def to(self, device):
+        return self
+
+    def __call__(self, points, boxes, masks):
+        assert points is None and masks is None
+        want = self.g[f"{self.tag}_call{self.k}_boxes"]
+        assert same(boxes.cpu().numpy(), want), (self.tag, self.k)
+        self.k += 1
+        n = boxes.shape[0]
+        return torch.zeros(n, 2, 4, device=DEV), torch.zeros(n, 4, *self.emb, device=DEV)
+
+    def get_dense_pe(self):
+        return torch.zeros(1, 4, *self.emb, device=DEV)
+
+
+class DecoderReplay(torch.nn.Module):
+    def __init__(self, g, tag, place=cuda):
+        super().__init__()
+        self.g, self.tag, self.k, self.place = g, tag, 0, place
+
+    def forward(self, image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings,
+                multimask_output):
+        assert multimask_output is False and image_embeddings.shape[0] == 1
+        m, iou = self.g[f"{self.tag}_call{self.k}_masks"], self.g[f"{self.tag}_call{self.k}_iou"]
+        assert sparse_prompt_embeddings.shape[0] == m.shape[0]
+        self.k += 1
+        return self.place(m), self.place(iou)
+
+
+def run_fixture(g, tag, place=cuda):
+    """The module on the fixture's inputs -> (inputs, outputs, refiner, factory calls)."""
+    B = len(g["counts"])
+    H, W = (int(v) for v in g["image_size"])
+    enc, made = PromptReplay(g, tag, place), []
+
+    def factory(image_size, emb_size):
+        made.append((tuple(image_size), tuple(emb_size)))
+        return enc
+
+    r = tmr_amd.SAM_box_refiner(DecoderReplay(g, tag, place), factory)
+    assert r.step == 50 and r.prompt_embed_dim == 256
+    r.step = int(g["step"])
+    ins = [[place(g[f"in_{what}{i}"]) for i in range(B)] for what in ("logits", "boxes", "refs")]
+    image = torch.zeros(B, 3, H, W, device=DEV)
+    feats = torch.zeros(B, 2, *(int(v) for v in g["emb_size"]), device=DEV)
+    if tag == "fwd":
+        out = r(ins[0], ins[1], ins[2], image, feats)
+    else:
+        out = r.forward_refine(ins[0], ins[1], ins[2], image, place(g["exemplars"]), feats)
+    assert enc.k == r.mask_decoder.k == int(g[f"{tag}_ncalls"])
+    return ins, out, r, made
+
+
+@pytest.mark.parametrize("tag", ["fwd", "rfn"])
+def test_module_reproduces_reference(golden, tag):
+    g = golden("refine")
+    ins, out, r, made = run_fixture(g, tag)
+    H, W = (int(v) for v in g["image_size"])
+    assert made == [((H, W), tuple(int(v) for v in g["emb_size"]))], "one prompt encoder per size pair"
+    assert len(out) == 3 and all(len(o) == len(g["counts"]) for o in out)
+    for i, n in enumerate(g["counts"]):
+        for o, what, cols in zip(out, ("logits", "boxes", "refs"), (2, 4, 2)):
+            assert o[i].dtype == torch.float32 and tuple(o[i].shape) == (n, cols) and o[i].device == DEV
+            assert same(o[i].cpu().numpy(), g[f"{tag}_{what}{i}"]), (tag, what, i)
+    for o, src in zip(out, ins):  # the image without candidates passes through: the same objects
+        assert o[3] is src[3]
+    if tag == "rfn":
+        assert np.isnan(out[1][1].cpu().numpy()).any()  # 0 * inf: IEEE carries through
+
+
+def test_forward_refine_empty_exemplar_mask_raises(golden):
+    g = dict(golden("refine"))
+    k = chunks(g, "rfn")[1][0]
+    g[f"rfn_call{k}_masks"] = -np.abs(g[f"rfn_call{k}_masks"]) - 1.0
+    with pytest.raises(ValueError):
+        run_fixture(g, "rfn")
+
+
+# ------------------------------------------------------------------ mask_boxes vs the restatement
+SHAPES = [(8, 12, 29, 45), (16, 16, 64, 64), (5, 7, 1, 9), (12, 9, 7, 4), (1, 1, 6, 6)]
+
+
+def draw_masks(seed, N, h, w, size, value_fn=None):
+    """N blob masks, each re-drawn until refine_ref.margin_ok holds for it."""
+    rng = np.random.default_rng(seed)
+    out = []
+    while len(out) < N:
+        m = refine_ref.blob_masks(rng, 1, h, w)
+        if refine_ref.margin_ok(m, size, value_fn):
+            out.append(m[0])
+    return np.stack(out)
+
+
+def corner_masks(h, w):
+    """All negative, all positive, and one positive low-res pixel in each corner."""
+    ms = [np.full((h, w), -0.7, f32), np.full((h, w), 0.3, f32)]
+    for y, x in ((0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1)):
+        m = np.full((h, w), -0.7, f32)
+        m[y, x] = 1.0
+        ms.append(m)
+    return np.stack(ms)
+
+
+def rows_for(rng, N):
+    lg = rng.uniform(-2, 2, (N, 2)).astype(f32)
+    if N:
+        lg[0, 1] = np.inf  # 0 * inf
+    return lg, rng.uniform(0.1, 1, (N, 1)).astype(f32)
+
+
+def check_against_ref(masks, size, lg, iou, scaler=None, place=cuda):
+    got = tmr_amd.mask_boxes(place(masks), size, place(lg), place(iou), None if scaler is None else place(scaler))
+    want = refine_ref.mask_boxes(masks, size, lg, iou, scaler)
+    for a, b, what in zip(got, want, ("logits", "boxes", "refs")):
+        assert a.dtype == torch.float32 and a.device == DEV
+        assert same(a.cpu().numpy(), b), (what, size, masks.shape)
+    return got
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_mask_boxes_equals_restatement(shape):
+    h, w, H, W = shape
+    rng = np.random.default_rng(sum(shape))
+    masks = np.concatenate([draw_masks(100 + sum(shape), 61, h, w, (H, W)), corner_masks(h, w)])
+    assert masks.shape[0] == 67 and refine_ref.margin_ok(masks, (H, W))
+    lg, iou = rows_for(rng, 67)
+    scaler = np.array([1.25, 0.5, np.inf, 2.0], f32)
+    for N in (0, 1, 3, 67):
+        sel = slice(67 - N, 67)  # the degenerate masks are last: part of every N > 3
+        got = check_against_ref(masks[sel], (H, W), lg[sel], iou[sel])
+        assert tuple(got[1].shape) == (N, 4)
+        check_against_ref(masks[sel][:, None], (H, W), lg[sel], iou[sel].reshape(-1), scaler)  # [N,1,h,w], iou [N]
+    ib = refine_ref.int_boxes(masks[61:], (H, W))
+    assert tuple(ib[0]) == (0, 0, 0, 0) and tuple(ib[1]) == (0, 0, W - 1, H - 1)
+    assert ib[2][0] == 0 and ib[2][1] == 0
+    if H > 1:  # (a single output row samples the first mask row only)
+        assert ib[5][2] == W - 1 and ib[5][3] == H - 1
+
+
+def test_single_pixels_on_kernel_boundaries():
+    """One positive output pixel (identity size ratio: the output pixel IS
+    the low-res pixel) in each image corner, on either side of the kernel's
+    16-row bands, of a wave's 64 columns and of the block's 256-column stride."""
+    H, W = 40, 300
+    spots = [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (15, 255), (16, 256), (15, 63), (16, 64), (31, 299),
+             (32, 0), (17, 128)]
+    masks = np.full((len(spots) + 1, H, W), -10.0, f32)
+    for n, (y, x) in enumerate(spots):
+        masks[n, y, x] = 1.0
+    masks[-1, 15, 255] = masks[-1, 16, 256] = masks[-1, 32, 10] = 1.0  # a box across bands and strides
+    rng = np.random.default_rng(5)
+    lg, iou = rows_for(rng, masks.shape[0])
+    got = check_against_ref(masks, (H, W), lg, iou)
+    ib = refine_ref.int_boxes(masks, (H, W))
+    for n, (y, x) in enumerate(spots):
+        assert tuple(ib[n]) == (x, y, x, y)
+    assert tuple(ib[-1]) == (10, 15, 256, 32)
+    assert same(got[1].cpu().numpy(), ib.astype(f32) / np.array([W, H, W, H], f32))
+    # the same pixels through a 4x ratio: a plus-shaped neighbourhood of each stays negative
+    h, w = 11, 76
+    m4 = np.full((len(spots), h, w), -10.0, f32)
+    for n, (y, x) in enumerate(spots):
+        m4[n, y // 4, x // 4] = 1.0
+    check_against_ref(m4, (4 * (h - 1) + 1, 4 * (w - 1) + 1), lg[:-1], iou[:-1])
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf])
+def test_non_finite_corner(bad):
+    """A NaN corner is evaluated literally (its pixels are not positive, its
+    neighbours' values are NaN too); a +inf corner gives +inf or, against a
+    zero weight, NaN.  Compared with the restatement only."""
+    h, w, H, W = 8, 12, 29, 45
+    masks = draw_masks(77, 6, h, w, (H, W))
+    masks[0, 3, 4] = bad
+    masks[1, 0, 0] = bad
+    masks[2, h - 1, w - 1] = bad
+    masks[3] = -1.0
+    masks[3, 5, 6] = bad  # the only candidate for a positive pixel
+    masks[4, :, :] = bad
+    rng = np.random.default_rng(9)
+    lg, iou = rows_for(rng, 6)
+    check_against_ref(masks, (H, W), lg, iou)
+    check_against_ref(masks, (H, W), lg, iou, np.array([0.5, 2.0, 1.0, 3.0], f32))
+
+
+def test_cpu_tensor_and_bad_shapes_raise():
+    with pytest.raises(tmr_amd.TMRError):
+        tmr_amd.mask_boxes(torch.zeros(1, 4, 4), (8, 8), torch.zeros(1, 2, device=DEV), torch.zeros(1, device=DEV))
+    z = torch.zeros(2, 4, 4, device=DEV)
+    with pytest.raises(tmr_amd.TMRError):
+        tmr_amd.mask_boxes(z, (8, 8), torch.zeros(3, 2, device=DEV), torch.zeros(2, device=DEV))
+    with pytest.raises(tmr_amd.TMRError):  # TMR_E_INVALID: wider than the kernel stages
+        tmr_amd.mask_boxes(torch.zeros(1, 2, 4097, device=DEV), (8, 8), torch.zeros(1, 2, device=DEV),
+                           torch.zeros(1, device=DEV))
+
+
+# ------------------------------------------------------------------ the workload's size
+def torch_boxes(pos):
+    """[N,H,W] bool -> int64 [N,4] (min X, min Y, max X, max Y), zeros when empty (device)."""
+    rows, cols = pos.any(2), pos.any(1)
+
+    def first(b):
+        return b.to(torch.uint8).argmax(1)
+
+    def last(b):
+        return b.shape[1] - 1 - b.flip(1).to(torch.uint8).argmax(1)
+
+    box = torch.stack([first(cols), first(rows), last(cols), last(rows)], 1)
+    box[~rows.any(1)] = 0
+    return box
+
+
+def test_workload_size_equals_materialised_torch():
+    """50 x 256^2 -> 1024^2: F.interpolate(align_corners=True) + threshold +
+    min / max on the same device."""
+    N, h, H = 50, 256, 1024
+    rng = np.random.default_rng(2024)
+    masks = cuda(refine_ref.blob_masks(rng, N, h, h))
+    for _ in range(20):  # re-draw the masks whose box would rest on rounding
+        v = F.interpolate(masks[:, None], (H, H), mode="bilinear", align_corners=True)[:, 0]
+        eps = (1e-5 * masks.abs().amax(dim=(1, 2)))[:, None, None]
+        want = torch_boxes(v > 0)
+        tight = ((torch_boxes(v > eps) == want) & (torch_boxes(v > -eps) == want)).all(1).cpu().numpy()
+        if tight.all():
+            break
+        for n in np.flatnonzero(~tight):
+            masks[n] = cuda(refine_ref.blob_masks(rng, 1, h, h)[0])
+    assert tight.all()
+    want = want.cpu().numpy()
+    assert (want[:, 2] > want[:, 0]).sum() > N // 2  # real boxes, not empties
+    lg, iou = rows_for(rng, N)
+    out_l, out_b, out_r = tmr_amd.mask_boxes(masks[:, None], (H, H), cuda(lg), cuda(iou))
+    exp_b = want.astype(f32) / np.array([H, H, H, H], f32)
+    assert same(out_b.cpu().numpy(), exp_b)
+    assert same(out_r.cpu().numpy(), np.stack([(exp_b[:, 0] + exp_b[:, 2]) / f32(2), (exp_b[:, 1] + exp_b[:, 3]) / f32(2)], 1))
+    with np.errstate(invalid="ignore"):
+        assert same(out_l.cpu().numpy(), np.stack([iou[:, 0] * lg[:, 0], f32(0) * lg[:, 1]], 1))
+
+
+# ------------------------------------------------------------------ guarded allocator
+def _refine_flow(g):
+    def flow(a):
+        place = lambda x: a.place(np.ascontiguousarray(x))  # noqa: E731
+        out = {}
+        for tag in ("fwd", "rfn"):
+            _, res, _, _ = run_fixture(g, tag, place)
+            out[tag] = [[t.cpu().numpy() for t in lst] for lst in res]
+        h, w, H, W = SHAPES[0]
+        masks = np.concatenate([draw_masks(3, 61, h, w, (H, W)), corner_masks(h, w)])
+        lg, iou = rows_for(np.random.default_rng(4), 67)
+        out["fn"] = [t.cpu().numpy() for t in check_against_ref(masks, (H, W), lg, iou, place=place)]
+        out["fn_scaled"] = [t.cpu().numpy() for t in check_against_ref(masks, (H, W), lg, iou,
+                                                                       np.array([2, 0.5, 1, 3], f32), place=place)]
+        return out
+
+    return flow
+
+
+def _bits(a, b, path=""):
+    if isinstance(a, dict):
+        assert set(a) == set(b)
+        for k in a:
+            _bits(a[k], b[k], f"{path}.{k}")
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), path
+        for i, (x, y) in enumerate(zip(a, b)):
+            _bits(x, y, f"{path}[{i}]")
+    else:
+        assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), path
+
+
+def test_refine_route_under_guarded_allocator(golden):
+    """Unpatched, zero-poisoned and 0xFF-poisoned runs give the same bits (no
+    output element is left unwritten, nothing reads the uninitialised work
+    buffer) and no guard byte around any allocation is written."""
+    flow = _refine_flow(golden("refine"))
+    with ga.context(None, DEV) as a:
+        plain = flow(a)
+    for poison in (ga.POISON_ZERO, ga.POISON_FF):  # zero first
+        with ga.GuardedAlloc(poison, DEV) as a:
+            out = flow(a)
+            assert len(a.records) > 0
+            a.check()
+        _bits(plain, out, f"poison {poison:#x}")
+
+
+# ------------------------------------------------------------------ detect(refiner=...)
+class BoxPrompt:
+    """A prompt encoder stand-in that hands the boxes on as the sparse embedding."""
+
+    def to(self, device):
+        return self
+
+    def __call__(self, points, boxes, masks):
+        return boxes.reshape(-1, 2, 2), torch.zeros(boxes.shape[0], 1, 1, 1, device=boxes.device)
+
+    def get_dense_pe(self):
+        return torch.zeros(1, 1, 1, 1, device=DEV)
+
+
+class BoxDecoder(torch.nn.Module):
+    """Masks [n,1,24,32] that are positive in a neighbourhood of each prompt
+    box, and an iou that depends on the box: a deterministic function of the
+    call's inputs, so two runs over the same candidates see the same masks."""
+
+    def __init__(self, image_size):
+        super().__init__()
+        self.size, self.calls = image_size, 0
+
+    def forward(self, image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings,
+                multimask_output):
+        self.calls += 1
+        b = sparse_prompt_embeddings.reshape(-1, 4)
+        H, W = self.size
+        gy = ((torch.arange(24, device=b.device) + 0.5) / 24 * H)[None, :, None]
+        gx = ((torch.arange(32, device=b.device) + 0.5) / 32 * W)[None, None, :]
+        cx, cy = ((b[:, 0] + b[:, 2]) / 2)[:, None, None], ((b[:, 1] + b[:, 3]) / 2)[:, None, None]
+        hw, hh = ((b[:, 2] - b[:, 0]) / 2 + 3)[:, None, None], ((b[:, 3] - b[:, 1]) / 2 + 3)[:, None, None]
+        m = 1 - torch.maximum((gx - cx).abs() / hw, (gy - cy).abs() / hh)
+        return m[:, None], (0.55 + 0.4 * torch.cos(b.sum(1, keepdim=True)))
+
+
+@pytest.mark.parametrize("refine", [False, True], ids=["forward", "forward_refine"])
+def test_detect_with_refiner_equals_module_sequence(refine):
+    P = oracle.reference_weights(0, cin=32, emb=32)
+    P["objectness_head.head.0.bias"] = torch.tensor([0.5])
+    Pd = {k: v.to(DEV) for k, v in P.items()}
+    feats = cuda(synth.sam_features(11, 2, 32, 64, 64))
+    ex, _ = synth.exemplar_set(12, 2, 2, 128, 128, 3, 9)
+    image = torch.zeros(2, 3, 96, 128, device=DEV)
+    sam_feats = torch.zeros(2, 4, 6, 8, device=DEV)
+    eng = tmr_amd.TMREngine(Pd, tmr_amd.PathConfig(emb_dim=32))
+    r = eng.forward_units(feats, np.repeat(np.arange(2), 2), ex.reshape(-1, 4))
+    o, b = r["o"].clone(), r["b"].clone()
+    # a threshold that leaves a few percent of the pixels: hundreds of candidates, several chunks
+    thr = float(torch.sigmoid(o.double()).flatten().quantile(0.97))
+    iou_thr = 0.5
+    before = eng.detect(feats, ex, cls_ths=thr, iou_threshold=iou_thr)
+    before = [[t.cpu().numpy() for t in lst] for lst in before]
+
+    dec = BoxDecoder((96, 128))
+    refiner = tmr_amd.SAM_box_refiner(dec, lambda image_size, emb_size: BoxPrompt())
+    rex = cuda(ex[:, :1]) if refine else None
+    got = eng.detect(feats, ex, cls_ths=thr, iou_threshold=iou_thr, refiner=refiner, image=image,
+                     sam_features=sam_feats, refine_exemplars=rex)
+    got = [[t.cpu().numpy() for t in lst] for lst in got]
+    calls = dec.calls
+
+    # the module-level sequence of trainer.py:95-118
+    batch = {"regression_ablation_b": False, "regression_ablation_c": False}
+    L, Bx, R = [], [], []
+    for i in range(2):
+        parts = []
+        for e in range(2):
+            u = 2 * i + e
+            parts.append(tmr_amd.Get_pred_boxes([o[u:u + 1]], [b[u:u + 1]], [[cuda(ex[i, e])]], batch, thr, True))
+        L.append(torch.cat([p[0][0] for p in parts]))
+        Bx.append(torch.cat([p[1][0] for p in parts]))
+        R.append(torch.cat([p[2][0] for p in parts]))
+    n_cand = [int(x.shape[0]) for x in L]
+    assert min(n_cand) > 50, n_cand  # more than one chunk per image
+    if refine:
+        L, Bx, R = refiner.forward_refine(L, Bx, R, image, rex, sam_feats)
+    else:
+        L, Bx, R = refiner(L, Bx, R, image, sam_feats)
+    L, Bx, R = tmr_amd.NMS(L, Bx, R, iou_thr)
+    assert dec.calls == 2 * calls
+    for lst, want in zip(got, (L, Bx, R)):
+        assert len(lst) == 2
+        for a, w_ in zip(lst, want):
+            assert same(a, w_.cpu().numpy())
+    assert any(not same(a, b_) for a, b_ in zip(got[1], before[1])), "the refiner changed the boxes"
+
+    # without a refiner: what detect returned before one existed
+    after = eng.detect(feats, ex, cls_ths=thr, iou_threshold=iou_thr)
+    for lst, want in zip(after, before):
+        for a, w_ in zip(lst, want):
+            assert same(a.cpu().numpy(), w_)
