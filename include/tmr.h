@@ -163,6 +163,30 @@ typedef struct tmr_xcorr_args {
     int32_t algo, min_k, prec, out_bf16;
 } tmr_xcorr_args_t;
 int tmr_xcorr(const tmr_xcorr_args_t *args, void *stream);
+/* Which kernel tmr_xcorr(args) would launch, from the host: the same
+ * validation and dispatch rule (tmr_xcorr itself decides through it), nothing
+ * launched, no device pointer dereferenced (the pointer fields are only
+ * compared with NULL).  Returns what tmr_xcorr returns before its first
+ * launch: TMR_OK with *plan filled, else TMR_E_INVALID / TMR_E_UNSUPPORTED
+ * with *plan zeroed.
+ *  kernel: TMR_XCORR_KERNEL_VALU the generic fp32 kernel (W % 4 != 0 or a
+ *   template wider than 31), _ROWS15 / _ROWS31 the row-tiled fp32 kernel's
+ *   width specialisations (max_wt <= 15 / <= 31), _MFMA the window kernel;
+ *  band_rows: output rows per block -- MFMA: 64 where the band, its halo and
+ *   the 3 over-rows fit the staging registers ((67 + 2 (max_ht / 2)) * W <=
+ *   16384 floats) and the band's LDS planes leave two blocks per CU (<= 78 KB),
+ *   else 32; VALU: 32, fewer where the staged rows would pass 150 KB of LDS
+ *   (TMR_E_UNSUPPORTED below one row);
+ *  col_groups: W / 64 accumulator groups per row quad (MFMA), else 0;
+ *  out16: the bf16-plane instantiation (args->out_bf16). */
+#define TMR_XCORR_KERNEL_VALU 0
+#define TMR_XCORR_KERNEL_ROWS15 1
+#define TMR_XCORR_KERNEL_ROWS31 2
+#define TMR_XCORR_KERNEL_MFMA 3
+typedef struct tmr_xcorr_plan {
+    int32_t kernel, band_rows, col_groups, out16;
+} tmr_xcorr_plan_t;
+int tmr_xcorr_plan(const tmr_xcorr_args_t *args, tmr_xcorr_plan_t *plan);
 /* Operand prep of the MFMA correlation: per (unit u, channel c) template
  * T [h = ht][w = wt] = templates[units[u].tmpl_offset + c*h*w ...], x = t * 2^-e
  * (one fp32 product, exact short of fp32 underflow) with 2^-e = the scale of

@@ -2,7 +2,7 @@
  * step of the SAM box refiner (reference utils/box_refine.py:158-176, 232-246).
  *
  * Not part of the core ABI of tmr.h (TMR_ABI_VERSION is unchanged by it): one
- * entry point, exported by the same libtmr.so, for callers that run the
+ * entry point and its host-side plan query, exported by the same libtmr.so, for callers that run the
  * reference's --refine_box evaluation.  The mask decoder and the prompt
  * encoder stay the caller's modules; this is what follows them.
  *
@@ -80,6 +80,20 @@ typedef struct tmr_mask_boxes_args {
 
 /* stream: a hipStream_t.  Returns TMR_OK or a TMR_E_* code of tmr.h. */
 int tmr_mask_boxes(const tmr_mask_boxes_args_t *args, void *stream);
+
+/* The launch geometry tmr_mask_boxes(args) would use, from the host: the same
+ * validation and band rule (tmr_mask_boxes itself decides through it), nothing
+ * launched, no buffer dereferenced.  Returns what tmr_mask_boxes returns
+ * before its first launch; on TMR_OK (N = 0 included, whatever the pointers):
+ *  band_rows: output rows per block -- 16, lowered until the low-resolution
+ *   rows such a band can touch, rows(tb) = (tb == 1) ? 2 :
+ *   (int)((double)(h - 1) / (H - 1) * (tb - 1) + 0.25) + 3, times w fit the
+ *   8192 staged floats;
+ *  cap_rows: 8192 / w, the most rows a band stages (>= 2);
+ *  nbands: ceil(H / band_rows), blocks per mask.
+ * Otherwise the three are zero. */
+int tmr_mask_boxes_plan(const tmr_mask_boxes_args_t *args, int32_t *band_rows, int32_t *cap_rows,
+                        int32_t *nbands);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,15 @@ class XcorrArgs(ctypes.Structure):
                 ("prec", ctypes.c_int32), ("out_bf16", ctypes.c_int32)]
 
 
+class XcorrPlan(ctypes.Structure):
+    """tmr_xcorr_plan_t (include/tmr.h)."""
+    _fields_ = [("kernel", ctypes.c_int32), ("band_rows", ctypes.c_int32), ("col_groups", ctypes.c_int32),
+                ("out16", ctypes.c_int32)]
+
+
+XCORR_KERNELS = {0: "valu", 1: "rows15", 2: "rows31", 3: "mfma"}  # TMR_XCORR_KERNEL_*
+
+
 class GtLossArgs(ctypes.Structure):
     """tmr_gt_loss_args_t (include/tmr.h)."""
     _fields_ = [("o", _P), ("reg", _P), ("boxes", _P), ("box_off", _P), ("units", _P), ("exp_table", _P),
@@ -105,6 +114,7 @@ SIGNATURES = {
     "tmr_templates": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "tmr_size": (_L, [_I, _L, _L, _L, _L, _L, _L]),
     "tmr_xcorr": (_I, [ctypes.POINTER(XcorrArgs), _P]),
+    "tmr_xcorr_plan": (_I, [ctypes.POINTER(XcorrArgs), ctypes.POINTER(XcorrPlan)]),
     "tmr_template_split": (_I, [_P, _P, _I, _I, _L, _I, _P, _P]),  # (..., total_rows, prec, out, stream)
     "tmr_heads_reduce": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "tmr_absmax_rows": (_I, [_P, _I, _L, _I, _P, _P]),
@@ -141,6 +151,8 @@ class MaskBoxesArgs(ctypes.Structure):
 EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_refine.h")
 EXT_SIGNATURES = {
     "tmr_mask_boxes": (_I, [ctypes.POINTER(MaskBoxesArgs), _P]),
+    "tmr_mask_boxes_plan": (_I, [ctypes.POINTER(MaskBoxesArgs), ctypes.POINTER(ctypes.c_int32),
+                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
 }
 REFINE_FORWARD, REFINE_SCALED = 0, 1  # tmr_mask_boxes_args_t.mode
 MASK_BOXES_WORK_PER_MASK = 16  # TMR_MASK_BOXES_WORK_BYTES(N) = 16 * N
@@ -238,6 +250,24 @@ def xcorr(stream=None, **fields) -> None:
     check(load().tmr_xcorr(ctypes.byref(_fill(XcorrArgs, "tmr_xcorr_args_t", fields)), stream), "tmr_xcorr")
 
 
+def xcorr_plan_rc(**fields):
+    """tmr_xcorr_plan(&args, &plan) -> (return code, (kernel name, band_rows, col_groups, out16) or None):
+    the kernel tmr_xcorr would launch for these fields; host only, nothing is launched."""
+    plan = XcorrPlan()
+    fields.pop("stream", None)
+    rc = load().tmr_xcorr_plan(ctypes.byref(_fill(XcorrArgs, "tmr_xcorr_args_t", fields)), ctypes.byref(plan))
+    if rc != 0:
+        return rc, None
+    return rc, (XCORR_KERNELS[plan.kernel], plan.band_rows, plan.col_groups, plan.out16)
+
+
+def xcorr_plan(**fields):
+    """xcorr_plan_rc's plan; raises TMRError where tmr_xcorr would refuse the launch."""
+    rc, plan = xcorr_plan_rc(**fields)
+    check(rc, "tmr_xcorr_plan")
+    return plan
+
+
 def gt_loss_args(**fields) -> GtLossArgs:
     return _fill(GtLossArgs, "tmr_gt_loss_args_t", fields)
 
@@ -251,6 +281,15 @@ def mask_boxes(stream_=None, **fields) -> None:
     """tmr_mask_boxes(&args, stream) (include/tmr_refine.h)."""
     check(load().tmr_mask_boxes(ctypes.byref(_fill(MaskBoxesArgs, "tmr_mask_boxes_args_t", fields)), stream_),
           "tmr_mask_boxes")
+
+
+def mask_boxes_plan(**fields):
+    """tmr_mask_boxes_plan(&args, ...) -> (band_rows, cap_rows, nbands); host only.  With N = 0 (the
+    default) the geometry of (h, w, H, W) alone, whatever the pointers."""
+    out = [ctypes.c_int32() for _ in range(3)]
+    check(load().tmr_mask_boxes_plan(ctypes.byref(_fill(MaskBoxesArgs, "tmr_mask_boxes_args_t", fields)),
+                                     *(ctypes.byref(o) for o in out)), "tmr_mask_boxes_plan")
+    return tuple(o.value for o in out)
 
 
 def require_gpu(t: torch.Tensor, name: str = "input") -> None:

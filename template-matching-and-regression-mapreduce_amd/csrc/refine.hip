@@ -208,24 +208,50 @@ __global__ __launch_bounds__(NT) void mask_boxes_epilogue_kernel(const int4 *__r
 
 }  // namespace
 
-extern "C" int tmr_mask_boxes(const tmr_mask_boxes_args_t *args, void *stream) {
+// The one statement of tmr_mask_boxes' validation and band rule (host only:
+// no buffer is dereferenced).  *launch stays false for the N = 0 no-op.
+static int mask_boxes_plan(const tmr_mask_boxes_args_t *args, int *tb_out, int *cap_rows_out, int *nbands_out,
+                           bool *launch) {
+    *launch = false;
     TMR_REQUIRE(args);
     const tmr_mask_boxes_args_t &a = *args;
     TMR_REQUIRE(a.N >= 0);
     TMR_REQUIRE(a.h >= 1 && a.h <= DIM_MAX && a.w >= 1 && a.w <= W_LOW_MAX);
     TMR_REQUIRE(a.H >= 1 && a.H <= DIM_MAX && a.W >= 1 && a.W <= DIM_MAX);
     TMR_REQUIRE(a.mode == TMR_REFINE_FORWARD || a.mode == TMR_REFINE_SCALED);
+    // the tallest band whose low-resolution rows fit the LDS stage
+    int tb = TB_MAX;
+    while (tb > 1 && (int64_t)band_rows(tb, a.h, a.H) * a.w > LDS_FLOATS) --tb;
+    *tb_out = tb;
+    *cap_rows_out = LDS_FLOATS / a.w;  // >= 2
+    *nbands_out = (int)tmr_cdiv(a.H, tb);
     if (a.N == 0) return TMR_OK;
     TMR_REQUIRE(a.masks && a.logits && a.iou && a.boxes && a.refs && a.logits_out && a.work);
     TMR_REQUIRE(a.mode == TMR_REFINE_FORWARD || a.scaler);
     TMR_REQUIRE((reinterpret_cast<uintptr_t>(a.work) & 15) == 0);
+    TMR_REQUIRE(a.N * *nbands_out < (1ll << 31));
+    *launch = true;
+    return TMR_OK;
+}
 
-    // the tallest band whose low-resolution rows fit the LDS stage
-    int tb = TB_MAX;
-    while (tb > 1 && (int64_t)band_rows(tb, a.h, a.H) * a.w > LDS_FLOATS) --tb;
-    const int cap_rows = LDS_FLOATS / a.w;  // >= 2
-    const int nbands = (int)tmr_cdiv(a.H, tb);
-    TMR_REQUIRE(a.N * nbands < (1ll << 31));
+extern "C" int tmr_mask_boxes_plan(const tmr_mask_boxes_args_t *args, int32_t *band_rows_out, int32_t *cap_rows,
+                                   int32_t *nbands) {
+    TMR_REQUIRE(band_rows_out && cap_rows && nbands);
+    int tb = 0, cap = 0, nb = 0;
+    bool launch;
+    const int rc = mask_boxes_plan(args, &tb, &cap, &nb, &launch);
+    *band_rows_out = rc == TMR_OK ? tb : 0;
+    *cap_rows = rc == TMR_OK ? cap : 0;
+    *nbands = rc == TMR_OK ? nb : 0;
+    return rc;
+}
+
+extern "C" int tmr_mask_boxes(const tmr_mask_boxes_args_t *args, void *stream) {
+    int tb = 0, cap_rows = 0, nbands = 0;
+    bool launch;
+    const int rc = mask_boxes_plan(args, &tb, &cap_rows, &nbands, &launch);
+    if (rc != TMR_OK || !launch) return rc;
+    const tmr_mask_boxes_args_t &a = *args;
     const unsigned nblk = (unsigned)tmr_cdiv(a.N, NT);
     const float sy = a.H > 1 ? (float)(a.h - 1) / (float)(a.H - 1) : 0.0f;
     const float sx = a.W > 1 ? (float)(a.w - 1) / (float)(a.W - 1) : 0.0f;

@@ -1090,21 +1090,20 @@ static int band_rows(int W, int max_ht, int prec) {
 }
 
 static int launch_mfma(const XArgs &a, hipStream_t s, int B, int max_ht, const void *tmpl_split,
-                       int64_t total_rows, int prec, bool out16) {
+                       int64_t total_rows, int prec, const tmr_xcorr_plan_t &plan) {
     MArgs m;
-    m.BR = band_rows(a.W, max_ht, prec);
+    m.BR = plan.band_rows;
     m.HG = max_ht / 2;
     m.LR = m.BR + 2 * m.HG + WIN_OVER;
     m.SB = band_stride(a.W / 64);
     m.nband = (int)tmr_cdiv(a.H, m.BR);
-    const int64_t nlog = (int64_t)m.nband * a.C * B;
-    TMR_REQUIRE(nlog < (1LL << 31) - 8);
-    m.nlog = (int)nlog;
+    m.nlog = (int)((int64_t)m.nband * a.C * B);  // < 2^31 - 8: xcorr_plan
     const size_t lds = (prec == TMR_PREC_F16X3 ? 2 : 1) * (size_t)m.LR * m.SB + 64 + 4 * UMAX;
-    const unsigned nblk = (unsigned)((nlog + 7) / 8 * 8);
+    const unsigned nblk = (unsigned)(((int64_t)m.nlog + 7) / 8 * 8);
     const _Float16 *trows = reinterpret_cast<const _Float16 *>(tmpl_split);
     const int32_t *texp = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(tmpl_split) +
                                                             (int64_t)a.C * total_rows * 2 * AFRAG);
+    const bool out16 = plan.out16 != 0;
     return m.BR == 64 ? launch_mfma_p<4>(a, m, lds, nblk, s, trows, texp, prec, out16)
                       : launch_mfma_p<2>(a, m, lds, nblk, s, trows, texp, prec, out16);
 }
@@ -1128,7 +1127,11 @@ extern "C" int tmr_template_split(const float *templates, const tmr_unit_t *unit
     return TMR_OK;
 }
 
-extern "C" int tmr_xcorr(const tmr_xcorr_args_t *x, void *stream) {
+// The one statement of tmr_xcorr's validation and dispatch rule (host only:
+// no pointer is dereferenced but x itself): which kernel a launch runs and
+// its band height.  tmr_xcorr launches what this returns; tmr_xcorr_plan
+// hands it to the caller.
+static int xcorr_plan(const tmr_xcorr_args_t *x, tmr_xcorr_plan_t *p) {
     TMR_REQUIRE(x);
     const int B = x->B, C = x->C, H = x->H, W = x->W, U = x->U, max_ht = x->max_ht, max_wt = x->max_wt;
     TMR_REQUIRE(x->f && x->templates && x->units && x->img_units && x->scale && x->out && B > 0 && C > 0 &&
@@ -1142,6 +1145,45 @@ extern "C" int tmr_xcorr(const tmr_xcorr_args_t *x, void *stream) {
     TMR_REQUIRE(x->algo >= TMR_XCORR_AUTO && x->algo <= TMR_XCORR_MFMA);
     TMR_REQUIRE(x->prec == TMR_PREC_F16X3 || x->prec == TMR_PREC_BF16 || x->prec == TMR_PREC_F16);
     TMR_REQUIRE(C < 65536 && B < 65536);
+    // the MFMA kernel reads its A fragments from tmpl_split (tmr_template_split)
+    const bool fits = mfma_fits(H, W, max_ht, max_wt) && x->tmpl_split && x->total_rows > 0;
+    if (x->algo == TMR_XCORR_MFMA && !fits) return TMR_E_UNSUPPORTED;
+    const bool use_mfma = x->algo == TMR_XCORR_MFMA || (x->algo == TMR_XCORR_AUTO && fits && x->min_k >= kMfmaMinK);
+    if (use_mfma) {
+        p->kernel = TMR_XCORR_KERNEL_MFMA;
+        p->band_rows = band_rows(W, max_ht, x->prec);
+        p->col_groups = W / 64;  // 1..4 (mfma_fits)
+        p->out16 = x->out_bf16;
+        TMR_REQUIRE(tmr_cdiv(H, p->band_rows) * C * B < (1LL << 31) - 8);
+        return TMR_OK;
+    }
+    TMR_REQUIRE(!x->out_bf16);
+    // row-tiled kernel when rows are 16-B aligned and templates fit its
+    // width specialisations (template sizes are odd, template_matching.py:66-73)
+    const bool rows = (W % 4) == 0 && max_wt <= 31;
+    const int WS = rows ? W + PADL + PADR : W;
+    // LDS rows: band + template halo + slack rows for partial 4-row tiles
+    const int max_rows = (150 * 1024) / (4 * WS) - 1;
+    const int RB = min(32, max_rows - (max_ht - 1) - (rows ? TRY + 3 : RY));
+    if (RB < 1) return TMR_E_UNSUPPORTED;
+    p->kernel = !rows ? TMR_XCORR_KERNEL_VALU : max_wt <= 15 ? TMR_XCORR_KERNEL_ROWS15 : TMR_XCORR_KERNEL_ROWS31;
+    p->band_rows = RB;
+    p->col_groups = 0;
+    p->out16 = 0;
+    return TMR_OK;
+}
+
+extern "C" int tmr_xcorr_plan(const tmr_xcorr_args_t *args, tmr_xcorr_plan_t *plan) {
+    TMR_REQUIRE(plan);
+    *plan = tmr_xcorr_plan_t{};
+    return xcorr_plan(args, plan);
+}
+
+extern "C" int tmr_xcorr(const tmr_xcorr_args_t *x, void *stream) {
+    tmr_xcorr_plan_t plan{};
+    const int prc = xcorr_plan(x, &plan);
+    if (prc != TMR_OK) return prc;
+    const int B = x->B, C = x->C, H = x->H, W = x->W, U = x->U, max_ht = x->max_ht;
     XArgs a;
     a.f = x->f;
     a.tmpl = x->templates;
@@ -1157,29 +1199,19 @@ extern "C" int tmr_xcorr(const tmr_xcorr_args_t *x, void *stream) {
     a.W = W;
     a.squeeze = x->squeeze;
     hipStream_t s = tmr_stream(stream);
-    // the MFMA kernel reads its A fragments from tmpl_split (tmr_template_split)
-    const bool fits = mfma_fits(H, W, max_ht, max_wt) && x->tmpl_split && x->total_rows > 0;
-    if (x->algo == TMR_XCORR_MFMA && !fits) return TMR_E_UNSUPPORTED;
-    const bool use_mfma = x->algo == TMR_XCORR_MFMA || (x->algo == TMR_XCORR_AUTO && fits && x->min_k >= kMfmaMinK);
-    if (use_mfma) {
-        const int rc = launch_mfma(a, s, B, max_ht, x->tmpl_split, x->total_rows, x->prec, x->out_bf16 != 0);
+    if (plan.kernel == TMR_XCORR_KERNEL_MFMA) {
+        const int rc = launch_mfma(a, s, B, max_ht, x->tmpl_split, x->total_rows, x->prec, plan);
         if (rc != TMR_OK) return rc;
     } else {
-        TMR_REQUIRE(!x->out_bf16);
-        // row-tiled kernel when rows are 16-B aligned and templates fit its
-        // width specialisations (template sizes are odd, template_matching.py:66-73)
-        const bool rows = (W % 4) == 0 && max_wt <= 31;
+        const bool rows = plan.kernel != TMR_XCORR_KERNEL_VALU;
         const int WS = rows ? W + PADL + PADR : W;
-        // LDS rows: band + template halo + slack rows for partial 4-row tiles
-        const int max_rows = (150 * 1024) / (4 * WS) - 1;
-        const int RB = min(32, max_rows - (max_ht - 1) - (rows ? TRY + 3 : RY));
-        if (RB < 1) return TMR_E_UNSUPPORTED;
+        const int RB = plan.band_rows;
         a.RB = RB;
         a.LR = rows ? RB + max_ht + 3 : RB + max_ht - 1 + RY;
         a.HG = max_ht / 2;
         const size_t lds = (rows ? (size_t)a.LR * WS * sizeof(float)
                                  : ((size_t)a.LR * W + XSLACK) * sizeof(float)) + 4 * UMAX;
-        const bool narrow = max_wt <= 15;
+        const bool narrow = plan.kernel == TMR_XCORR_KERNEL_ROWS15;
         const void *kfn = !rows ? (const void *)xcorr_kernel
                           : narrow ? (const void *)xcorr_rows_kernel<15> : (const void *)xcorr_rows_kernel<31>;
         if (lds > 64 * 1024 && tmr_set_max_lds(kfn, lds) != hipSuccess) return TMR_E_HIP;

@@ -40,14 +40,41 @@ def upsample(mask, size):
         return hy[:, None] * top + ly[:, None] * bot
 
 
-def int_boxes(masks, size):
-    """[N,4] int64 (min X, min Y, max X, max Y) of v > 0; zeros when empty."""
+def upsample_contracted(mask, size):
+    """upsample with each `p * a + q * b` of the rule evaluated as ONE fused
+    multiply-add, fl32(p * a + fl32(q * b)) with the first product exact
+    (float64 holds the product of two fp32 values exactly, and its sum with an
+    fp32 value is rounded to fp32 once for all but double-rounding ties): what
+    a build that lost -ffp-contract=off would compute.  NOT the rule: the
+    host test counts the ramp masks whose box tells the two apart."""
+    m = np.asarray(mask, f32)
+    h, w = m.shape
+    H, W = size
+    y0, y1, ly, hy = _axis(h, H)
+    x0, x1, lx, hx = _axis(w, W)
+    f64 = np.float64
+
+    def fma(p, a, q, b):
+        return (p.astype(f64) * a.astype(f64) + (q * b).astype(f32).astype(f64)).astype(f32)
+
+    with np.errstate(invalid="ignore", over="ignore"):
+        a, b = m[y0][:, x0], m[y0][:, x1]
+        c, d = m[y1][:, x0], m[y1][:, x1]
+        top = fma(hx[None, :], a, lx[None, :], b)
+        bot = fma(hx[None, :], c, lx[None, :], d)
+        return fma(hy[:, None], top, ly[:, None], bot)
+
+
+def int_boxes(masks, size, value_fn=None):
+    """[N,4] int64 (min X, min Y, max X, max Y) of v > 0; zeros when empty.
+    value_fn(mask, size) gives v (default: upsample, the rule)."""
+    value_fn = value_fn or upsample
     masks = np.asarray(masks, f32)
     if masks.ndim == 4:
         masks = masks[:, 0]
     out = np.zeros((masks.shape[0], 4), np.int64)
     for n, m in enumerate(masks):
-        ys, xs = np.nonzero(upsample(m, size) > 0)
+        ys, xs = np.nonzero(value_fn(m, size) > 0)
         if ys.size:
             out[n] = (xs.min(), ys.min(), xs.max(), ys.max())
     return out
@@ -101,6 +128,36 @@ def blob_masks(rng, N: int, h: int, w: int):
             m += rng.uniform(5.0, 12.0) * np.exp(-((ys - cy) ** 2 / (2 * sy * sy) + (xs - cx) ** 2 / (2 * sx * sx)))
         out[n] = (m + 0.05 * rng.standard_normal((h, w))).astype(f32)
     return out
+
+
+def ramp_masks(h: int, w: int, H: int, W: int, x_stride: int = 1):
+    """Masks whose box rests on the last bits of v: for an output column X
+    (1 .. W-2, every x_stride-th) the plane m[y][x] = fl32(x) - c with
+    c = sx * fl32(X), sx = fl32(w-1) / fl32(W-1) as the rule computes it, and
+    its negation; likewise m[y][x] = fl32(y) - sy * fl32(Y) for every output
+    row Y in 1 .. H-2.  In exact arithmetic the interpolated value at column X
+    (row Y) is zero, so its sign -- whether that column belongs to the box --
+    is the rounding of the rule's own operation order: a fused multiply-add, a
+    reordered sum or a weight computed another way moves the box.  [N,h,w]."""
+    sx = f32(w - 1) / f32(W - 1) if W > 1 else f32(0.0)
+    sy = f32(h - 1) / f32(H - 1) if H > 1 else f32(0.0)
+    xs = np.broadcast_to(np.arange(w, dtype=f32)[None, :], (h, w))
+    ys = np.broadcast_to(np.arange(h, dtype=f32)[:, None], (h, w))
+    out = []
+    for X in range(1, W - 1, x_stride):
+        m = xs - sx * f32(X)
+        out += [m, -m]
+    for Y in range(1, H - 1):
+        m = ys - sy * f32(Y)
+        out += [m, -m]
+    return np.stack(out).astype(f32)
+
+
+# the ramp shapes of the refiner tests: (h, w, H, W), x_stride.  The last three
+# stage reduced bands (tmr_mask_boxes_plan): 11 rows with the staged rows at
+# their cap, 12 rows, and 1 row at the widest mask the kernel takes.
+RAMP_SHAPES = [((16, 16, 64, 64), 1), ((7, 11, 23, 37), 1), ((30, 700, 37, 900), 8), ((200, 100, 30, 45), 1),
+               ((3, 4096, 7, 50), 1)]
 
 
 def margin_ok(masks, size, value_fn=None) -> bool:

@@ -31,8 +31,8 @@ def test_library_exports_every_declared_symbol():
     L = tmr_amd.load()
     assert L.tmr_version() == 3
     # ABI 3: one correlation entry point, one sizing query, one
-    # split conv entry point -- at most ~25 symbols
-    assert len(syms) <= 25, syms
+    # split conv entry point -- at most ~25 symbols, and the correlation's host-only plan query
+    assert "tmr_xcorr_plan" in syms and len(syms) <= 26, syms
     assert L.tmr_strerror(0) == b"ok"
     assert b"invalid" in L.tmr_strerror(-1)
 
@@ -121,6 +121,84 @@ def test_invalid_arguments_return_codes():
     big = 700_000
     assert L.tmr_nms(a, a, a, a, a, a, a, a, 1, big, big, (big + 63) // 64, 0.5, a, a, a, None, a, a,
                      None) == -1
+
+
+def _plan_fields(**kw):
+    """tmr_xcorr_args_t fields for a host-only plan query: the pointers are only compared with NULL."""
+    some = 64
+    f = dict(f=some, templates=some, units=some, img_units=some, scale=some, out=some, tmpl_split=some,
+             total_rows=1, B=2, C=2, H=40, W=64, U=1, max_ht=1, max_wt=1, min_k=1, algo=_lib.XCORR_ALGOS["mfma"],
+             prec=_lib.PREC_CODES["fp32"])
+    f.update(kw)
+    return f
+
+
+def test_xcorr_plan_no_gpu():
+    """tmr_xcorr_plan: tmr_xcorr's own validation and dispatch, on the host."""
+    L = tmr_amd.load()
+    assert ctypes.sizeof(_lib.XcorrPlan) == 16
+    assert L.tmr_xcorr_plan(None, None) == -1
+    plan = _lib.XcorrPlan(9, 9, 9, 9)
+    assert L.tmr_xcorr_plan(None, ctypes.byref(plan)) == -1 and (plan.kernel, plan.band_rows) == (0, 0)
+    rc = _lib.xcorr_plan_rc
+    assert rc(**_plan_fields(f=None)) == (-1, None)  # what tmr_xcorr says of a NULL tensor
+    assert rc(**_plan_fields(W=192, max_ht=11)) == (0, ("mfma", 64, 3, 0))
+    assert rc(**_plan_fields(W=192, max_ht=13)) == (0, ("mfma", 32, 3, 0))
+    assert rc(**_plan_fields(W=192, max_ht=19, prec=1, out_bf16=1)) == (0, ("mfma", 64, 3, 1))
+    assert rc(**_plan_fields(W=192, max_ht=19, prec=2, out_bf16=1)) == (-1, None)  # the plane is bf16 only
+    assert rc(**_plan_fields(W=256, max_ht=31)) == (-3, None)  # past the staging registers
+    assert rc(**_plan_fields(W=256, max_ht=31, algo=0)) == (0, ("rows15", 32, 0, 0))  # auto: the VALU kernel
+    assert rc(**_plan_fields(W=96)) == (-3, None)
+    assert rc(**_plan_fields(W=96, algo=1, max_wt=17)) == (0, ("rows31", 32, 0, 0))
+    assert rc(**_plan_fields(W=97, algo=1)) == (0, ("valu", 32, 0, 0))
+    assert rc(**_plan_fields(tmpl_split=None)) == (-3, None)
+    assert rc(**_plan_fields(tmpl_split=None, algo=0)) == (0, ("rows15", 32, 0, 0))
+    assert rc(**_plan_fields(H=9, max_ht=11)) == (-1, None)  # a template taller than the map
+    # the VALU band shrinks where the staged rows pass 150 KB, down to a refusal
+    v = dict(algo=1, tmpl_split=None, total_rows=0)
+    assert rc(**_plan_fields(H=40, W=1024, max_ht=15, max_wt=15, **v)) == (0, ("rows15", 13, 0, 0))
+    assert rc(**_plan_fields(H=40, W=1024, max_ht=27, max_wt=31, **v)) == (0, ("rows31", 1, 0, 0))
+    assert rc(**_plan_fields(H=40, W=1024, max_ht=29, max_wt=31, **v)) == (-3, None)
+    assert rc(**_plan_fields(H=40, W=512, max_ht=31, max_wt=31, **v)) == (0, ("rows31", 31, 0, 0))
+    assert rc(**_plan_fields(H=40, W=1022, max_ht=31, max_wt=31, **v)) == (0, ("valu", 4, 0, 0))
+    with pytest.raises(tmr_amd.TMRError):
+        _lib.xcorr_plan(**_plan_fields(W=96))
+
+
+def test_xcorr_fixed_cases_cover_every_mfma_variant():
+    """Every MFMA instantiation tmr_xcorr can pick -- tmr_xcorr_plan scanned
+    over the four widths, every odd template height, the three precisions and
+    the bf16 output plane -- has a fixed-shape case in tests/xcorr_cases.py
+    (run, with its plan asserted, by tests/test_gpu_parity.py).  The reachable
+    set comes from the library: a retuned band rule that reaches a new
+    (band height, width) pair turns this red until a case names it."""
+    import xcorr_cases
+    reachable = set()
+    for W in (64, 128, 192, 256):
+        for mh in range(1, 32, 2):
+            for prec, o16 in (("fp32", 0), ("bf16", 0), ("f16", 0), ("bf16", 1)):
+                rc, plan = _lib.xcorr_plan_rc(**_plan_fields(W=W, max_ht=mh, prec=_lib.PREC_CODES[prec],
+                                                             out_bf16=o16))
+                if rc == 0:
+                    assert plan[0] == "mfma" and plan[2] == W // 64 and plan[3] == o16
+                    reachable.add((plan[1], plan[2], prec, o16))
+                else:
+                    assert rc == -3 and W == 256 and mh == 31, (W, mh, prec, o16, rc)
+    covered = xcorr_cases.mfma_variants_covered()
+    assert len(reachable) >= 16  # four widths x four precisions at the least
+    assert not reachable - covered, f"MFMA variants without a fixed case: {sorted(reachable - covered)}"
+    assert not covered - reachable, f"tests/xcorr_cases.py names unreachable variants: {sorted(covered - reachable)}"
+    # the table's literals are the library's answers at the cases' own shapes
+    for cases, precs in ((xcorr_cases.MFMA_3TERM, ("fp32",)), (xcorr_cases.MFMA_ONE_TERM, ("bf16", "f16"))):
+        for H, W, C, kmax, variant in cases:
+            for prec in precs:
+                got = _lib.xcorr_plan(**_plan_fields(H=H, W=W, C=C, max_ht=min(kmax, H // 2 * 2 - 1), max_wt=kmax,
+                                                     prec=_lib.PREC_CODES[prec]))
+                assert got == ("mfma",) + variant + (0,), (H, W, kmax, prec, got)
+    for H, W, (mh, mw), variant in xcorr_cases.VALU_REDUCED:
+        mh = min(mh, H // 2 * 2 - 1 if H % 2 == 0 else H)
+        got = _lib.xcorr_plan(**_plan_fields(H=H, W=W, max_ht=mh, max_wt=mw, algo=1))
+        assert got == variant + (0, 0) and got[1] < 32, (H, W, mh, mw, got)
 
 
 def test_tm_utils_host_helpers():

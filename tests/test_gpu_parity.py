@@ -16,6 +16,7 @@ import torch
 
 import oracle
 import tmr_amd
+import xcorr_cases
 from operand_ref import xrecords_ref as _xrecords_ref
 from tmr_amd import host, synth
 
@@ -1059,19 +1060,23 @@ def test_reduced_precision_forward_vs_oracle(prec):
 
 
 # ----------------------------------------------------------------- xcorr (MFMA)
-@pytest.mark.parametrize("H,W,C,kmax", [(128, 128, 16, 31), (70, 64, 24, 15), (70, 128, 8, 31),
-                                        (192, 192, 8, 31), (33, 64, 8, 15), (128, 128, 8, 15),
-                                        (100, 192, 8, 21), (77, 256, 8, 9), (40, 256, 8, 29)])
-def test_xcorr_mfma_vs_oracle(H, W, C, kmax):
-    """The row-Toeplitz MFMA correlation kernel (TMR_XCORR_MFMA, 3-term fp16
-    split) against the C oracle at every odd template side 1..31, rectangular
+def _case_id(case):
+    return "-".join(str(v) for v in case[:4])
+
+
+@pytest.mark.parametrize("H,W,C,kmax,variant", xcorr_cases.MFMA_3TERM, ids=[_case_id(c) for c in xcorr_cases.MFMA_3TERM])
+def test_xcorr_mfma_vs_oracle(H, W, C, kmax, variant):
+    """The window MFMA correlation kernel (TMR_XCORR_MFMA, 3-term fp16 split)
+    against the C oracle at every odd template side 1..31, rectangular
     templates, several units per image, band edges (H % 32 / % 64 != 0), a
     learned scale, relu output, the fused max |f_TM| and the zero pad border.
-    Both band heights run: 64-row bands where the band and halo fit the
-    staging registers (W 64 / 128, W 192 with kmax <= 21, W 256 with kmax <=
-    1), 32-row bands otherwise; every accumulator width (1-4 64-column
-    groups)."""
-    _xcorr_mfma_case(H, W, C, kmax, "fp32")
+    Every reachable (band height, accumulator width) pair runs, and each case
+    asserts the pair tmr_xcorr_plan names against its literal in
+    tests/xcorr_cases.py: 64-row bands where the band, its halo and the 3
+    over-rows fit the staging registers and two blocks fit a CU's LDS (W 64 /
+    128 at every template height, W 192 up to 11 rows), 32-row bands otherwise
+    (W 192 above that, W 256 always, up to 29 rows); 1-4 64-column groups."""
+    _xcorr_mfma_case(H, W, C, kmax, "fp32", variant)
 
 
 # bf16 MFMA path (BASELINE config C, north_star "within a stated bf16
@@ -1082,13 +1087,17 @@ XCORR_ONE_TERM_TOL = {"bf16": 1e-2, "f16": 2e-3}
 
 
 @pytest.mark.parametrize("prec", ["bf16", "f16"])
-@pytest.mark.parametrize("H,W,C,kmax", [(128, 128, 16, 31), (70, 64, 24, 15), (128, 128, 8, 15),
-                                        (100, 192, 8, 21)])
-def test_xcorr_mfma_one_term_vs_oracle(H, W, C, kmax, prec):
-    """tmr_xcorr with one bf16 / fp16 MFMA term: the same shapes, border,
-    relu and fused-max contract as the 3-term kernel, at the one-term tolerance;
-    the VALU kernel in the same call stays fp32 (1e-5)."""
-    _xcorr_mfma_case(H, W, C, kmax, prec)
+@pytest.mark.parametrize("H,W,C,kmax,variant", xcorr_cases.MFMA_ONE_TERM,
+                         ids=[_case_id(c) for c in xcorr_cases.MFMA_ONE_TERM])
+def test_xcorr_mfma_one_term_vs_oracle(H, W, C, kmax, variant, prec):
+    """tmr_xcorr with one bf16 / fp16 MFMA term: the same border, relu and
+    fused-max contract as the 3-term kernel, at the one-term tolerance; the
+    VALU kernel in the same call stays fp32 (1e-5).  One plane halves the
+    band's LDS, so 64-row bands reach 19-row templates at W 192; every
+    reachable (band height, accumulator width) pair has a case, asserted
+    against tmr_xcorr_plan, and the bf16 cases run the bf16 output plane's
+    instantiation of the same pair."""
+    _xcorr_mfma_case(H, W, C, kmax, prec, variant)
 
 
 XCORR_SWEEP = int(os.environ.get("TMR_XCORR_SWEEP", "24"))
@@ -1152,6 +1161,15 @@ def test_xcorr_mfma_random_sweep_vs_oracle(seed):
     got = out.cpu().numpy()
     assert np.array_equal(amax.cpu().numpy(), np.abs(got).reshape(U, -1).max(1))
     assert np.array_equal(relu.cpu().numpy(), np.maximum(got, 0))
+    if prec == "bf16":
+        # the bf16 output plane at the drawn shape (no relu output with it): RNE bf16 of the fp32 plane
+        o16 = torch.empty((U, C, H, W), device=DEV, dtype=torch.bfloat16)
+        amax16 = torch.zeros(U, device=DEV)
+        xcorr(f=ptr(fd), templates=ptr(tmpl), units=ptr(ud), img_units=ptr(iu), scale=ptr(scale), out=ptr(o16),
+              out_absmax=ptr(amax16), tmpl_split=ptr(tsplit), total_rows=rows, B=B, C=C, H=H, W=W, U=U, max_ht=mh,
+              max_wt=mw, min_k=1, algo=XCORR_ALGOS["mfma"], prec=pc, out_bf16=1, stream=stream())
+        torch.cuda.synchronize()
+        assert torch.equal(o16.view(torch.int16), out.to(torch.bfloat16).view(torch.int16)), (seed, H, W, C)
     tol = TOL if prec == "fp32" else XCORR_ONE_TERM_TOL[prec]
     tmpl_h = tmpl.cpu().numpy()
     for u in range(U):
@@ -1179,8 +1197,8 @@ def _xcorr_exact(f, t, scale):
     return out
 
 
-def _xcorr_mfma_case(H, W, C, kmax, prec):
-    from tmr_amd._lib import PREC_CODES, XCORR_ALGOS, call, ptr, size, stream, xcorr
+def _xcorr_mfma_case(H, W, C, kmax, prec, variant):
+    from tmr_amd._lib import PREC_CODES, XCORR_ALGOS, call, ptr, size, stream, xcorr, xcorr_plan
     from tmr_amd.graphs import _h2d, _units_to_device
     B = 2
     f = synth.normal(90 + H + W, (B, C, H, W)) * 1.7
@@ -1208,6 +1226,13 @@ def _xcorr_mfma_case(H, W, C, kmax, prec):
     common = dict(f=ptr(fd), templates=ptr(tmpl), units=ptr(ud), img_units=ptr(iu), scale=ptr(scale),
                   tmpl_split=ptr(tsplit), total_rows=rows, B=B, C=C, H=H, W=W, U=U, max_ht=mh, max_wt=mw,
                   min_k=1, stream=stream())
+    # the launch variant this case is in the table for (tests/xcorr_cases.py)
+    got_plan = xcorr_plan(out=ptr(fd), algo=XCORR_ALGOS["mfma"], prec=pc, **common)
+    assert got_plan == ("mfma",) + tuple(variant) + (0,), \
+        f"tests/xcorr_cases.py is stale: {H}x{W} kmax {kmax} {prec} now runs {got_plan}, the table says {variant}"
+    if prec == "bf16":
+        assert xcorr_plan(out=ptr(fd), algo=XCORR_ALGOS["mfma"], prec=pc, out_bf16=1, **common) == \
+            ("mfma",) + tuple(variant) + (1,)
     outs = {}
     for algo in ("valu", "mfma"):
         out = torch.empty((U, C, H, W), device=DEV)
@@ -1256,7 +1281,7 @@ def _xcorr_mfma_case(H, W, C, kmax, prec):
                 assert (got[u][:, :ph] == 0).all() and (got[u][:, H - ph:] == 0).all()
             if pw:
                 assert (got[u][:, :, :pw] == 0).all() and (got[u][:, :, W - pw:] == 0).all()
-    print(f"xcorr mfma {prec} {H}x{W}: worst normwise {worst:.3e}")
+    print(f"xcorr mfma {prec} {H}x{W} kmax {kmax} plan {got_plan}: worst normwise {worst:.3e}")
 
 
 def test_engine_bf16_ftm_plane_bitexact():
@@ -1286,6 +1311,124 @@ def test_engine_bf16_ftm_plane_bitexact():
         # the module form (relu(f_TM) returned) keeps the fp32 plane
         eng.forward_units(cuda(feats), ui, ex.reshape(-1, 4), want_aux=True)
         assert not eng.last_xcorr_out16
+
+
+@pytest.mark.parametrize("hf,wf", [(16, 96), (16, 128)], ids=["32x192", "32x256"])
+def test_engine_bf16_ftm_plane_bitexact_nonsquare(hf, wf):
+    """The bf16 f_TM plane on non-square maps, 32 x 192 and 32 x 256 (3 and 4
+    accumulator groups: the square-map test above runs 1 and 2 only): o and b
+    with engine.out_bf16 on are bit-identical to the fp32-plane path."""
+    cin, emb, B, E = 64, 128, 2, 3
+    P = synth.reference_state_dict(9, cin=cin, emb=emb, obj_bias=-0.3, k=3)
+    feats = synth.sam_features(170 + wf, B, cin, hf, wf)
+    ex, _ = synth.exemplar_set(171 + wf, B, E, 2 * hf, 2 * wf, 3, 15)
+    ui = np.repeat(np.arange(B), E)
+    res = {}
+    for mode in ("fp32", "plane"):
+        eng = tmr_amd.TMREngine({k_: cuda(v) for k_, v in P.items()},
+                                tmr_amd.PathConfig(emb_dim=emb, precision="bf16", decoder_kernel_size=3))
+        eng.xcorr_algo = "mfma"
+        eng.out_bf16 = mode != "fp32"
+        r = eng.forward_units(cuda(feats), ui, ex.reshape(-1, 4))
+        assert eng.last_xcorr_algo == "mfma" and eng.last_xcorr_out16 == (mode != "fp32")
+        res[mode] = (r["o"].cpu().numpy(), r["b"].cpu().numpy())
+        assert res[mode][0].shape[-2:] == (2 * hf, 2 * wf)
+    for a, b in zip(res["fp32"], res["plane"]):
+        assert np.isfinite(a).all() and bits_equal(a, b), (hf, wf)
+
+
+def _valu_units(H, W, mh, mw, C):
+    """Six units over two images with mixed rectangular odd templates, the
+    first of the largest size (mh x mw clamped to the map), and their random
+    taps: (units, templates, image of each unit)."""
+    hodd = H // 2 * 2 - 1 if H % 2 == 0 else H
+    shapes = [(mh, mw), (3, 3), (mh, 1), (7, 5), (1, mw), (13, 9)]
+    shapes = [(min(kh, mh, hodd), min(kw, mw)) for kh, kw in shapes]
+    ui = [0, 0, 0, 1, 1, 1]
+    units = np.zeros(len(shapes), tmr_amd._lib.UNIT_DTYPE)
+    off, taps = 0, []
+    for u, (kh, kw) in enumerate(shapes):
+        units["image"][u], units["ht"][u], units["wt"][u], units["tmpl_offset"][u] = ui[u], kh, kw, off
+        taps.append(synth.normal(500 + 31 * u + H + W, (C, kh, kw)))
+        off += C * kh * kw
+    return units, taps, ui
+
+
+@pytest.mark.parametrize("H,W,kmax,variant", xcorr_cases.VALU_REDUCED,
+                         ids=[f"{c[0]}x{c[1]}-{c[3][0]}-band{c[3][1]}" for c in xcorr_cases.VALU_REDUCED])
+def test_xcorr_valu_reduced_bands_vs_exact(H, W, kmax, variant):
+    """The fp32 VALU kernels on maps wider than 256 columns, where the staged
+    rows pass 150 KB of LDS and tmr_xcorr lowers the band below 32 output rows
+    (down to 1 row at 1024 columns with a 27-row template, 4 rows in the
+    generic kernel at 1022 columns with a 31-row one): the band the plan names
+    is asserted against tests/xcorr_cases.py, the maps against the exact
+    (float64) correlation at the fp32 contract, the zero border, and the
+    fused max and relu bit for bit."""
+    from tmr_amd._lib import PREC_CODES, XCORR_ALGOS, ptr, stream, xcorr, xcorr_plan
+    from tmr_amd.graphs import _h2d, _units_to_device
+    B, C = 2, 2
+    units, taps, ui = _valu_units(H, W, kmax[0], kmax[1], C)
+    U = len(ui)
+    mh, mw = int(units["ht"].max()), int(units["wt"].max())
+    f = synth.normal(40 + H + W, (B, C, H, W)) * 1.7
+    fd = cuda(f)
+    tmpl = cuda(np.concatenate([t.reshape(-1) for t in taps]))
+    ud = _units_to_device(units, DEV)
+    iu = _h2d(host.image_ranges(ui, B), DEV)
+    sc = 0.75
+    scale = torch.tensor([sc], device=DEV)
+    out = torch.empty((U, C, H, W), device=DEV)
+    relu = torch.empty_like(out)
+    amax = torch.zeros(U, device=DEV)
+    args = dict(f=ptr(fd), templates=ptr(tmpl), units=ptr(ud), img_units=ptr(iu), scale=ptr(scale), out=ptr(out),
+                relu_out=ptr(relu), out_absmax=ptr(amax), B=B, C=C, H=H, W=W, U=U, max_ht=mh, max_wt=mw, min_k=1,
+                algo=XCORR_ALGOS["valu"], prec=PREC_CODES["fp32"], stream=stream())
+    plan = xcorr_plan(**args)
+    assert plan == tuple(variant) + (0, 0), \
+        f"tests/xcorr_cases.py is stale: {H}x{W} templates <= {mh}x{mw} now run {plan}, the table says {variant}"
+    assert plan[1] < 32
+    xcorr(**args)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert np.array_equal(amax.cpu().numpy(), np.abs(got).reshape(U, -1).max(1))
+    assert np.array_equal(relu.cpu().numpy(), np.maximum(got, 0))
+    worst = 0.0
+    for u in range(U):
+        ht, wt = taps[u].shape[-2:]
+        err = normwise(got[u], _xcorr_exact(f[ui[u]], taps[u], sc))
+        worst = max(worst, err)
+        assert err <= TOL, (u, ht, wt, err)
+        ph, pw = ht // 2, wt // 2
+        if ph:
+            assert (got[u][:, :ph] == 0).all() and (got[u][:, H - ph:] == 0).all()
+        if pw:
+            assert (got[u][:, :, :pw] == 0).all() and (got[u][:, :, W - pw:] == 0).all()
+        assert np.abs(got[u]).max() > 0
+    print(f"xcorr valu {H}x{W} templates <= {mh}x{mw} plan {plan}: worst normwise {worst:.3e}")
+
+
+def test_xcorr_valu_refuses_band_below_one_row():
+    """1024 columns with a 29-row template leave no output row in 150 KB of
+    LDS: tmr_xcorr_plan says TMR_E_UNSUPPORTED and tmr_xcorr raises, on the
+    host, before anything is launched (the output keeps its bytes).  On a
+    9-row map such a template is refused as well (taller than the map)."""
+    from tmr_amd._lib import PREC_CODES, XCORR_ALGOS, ptr, stream, xcorr, xcorr_plan_rc
+    C, W = 2, 1024
+    for H, want in ((33, -3), (9, -1)):
+        fd = torch.zeros((1, C, H, W), device=DEV)
+        tmpl = torch.zeros(C * 29 * 3, device=DEV)
+        out = torch.full((1, C, H, W), 7.0, device=DEV)
+        meta = torch.zeros(64, device=DEV, dtype=torch.int32)  # never read: the refusal comes first
+        args = dict(f=ptr(fd), templates=ptr(tmpl), units=ptr(meta), img_units=ptr(meta), scale=ptr(tmpl),
+                    out=ptr(out), B=1, C=C, H=H, W=W, U=1, max_ht=29, max_wt=3, min_k=1,
+                    algo=XCORR_ALGOS["valu"], prec=PREC_CODES["fp32"], stream=stream())
+        assert xcorr_plan_rc(**args) == (want, None)
+        with pytest.raises(tmr_amd.TMRError):
+            xcorr(**args)
+        torch.cuda.synchronize()
+        assert (out == 7.0).all()
+    # one row fewer in the template fits: a 1-row band
+    assert xcorr_plan_rc(**dict(args, H=33, max_ht=27)) == (0, ("rows15", 1, 0, 0))
 
 
 def test_xcorr_mfma_refuses_other_widths():

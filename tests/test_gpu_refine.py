@@ -213,6 +213,116 @@ def test_single_pixels_on_kernel_boundaries():
     check_against_ref(m4, (4 * (h - 1) + 1, 4 * (w - 1) + 1), lg[:-1], iou[:-1])
 
 
+# ------------------------------------------------------------------ every band geometry
+# (h, w, H, W) -> tmr_mask_boxes_plan's (band rows, staged-row cap, bands per mask) where the band is
+# lowered below 16 rows: 11 rows with the staged rows AT their cap, 12 rows, 1 row at the widest mask
+REDUCED_BANDS = {(30, 700, 37, 900): (11, 11, 4), (200, 100, 30, 45): (12, 81, 3), (3, 4096, 7, 50): (1, 2, 7)}
+
+
+def assert_plan(shape, want):
+    h, w, H, W = shape
+    plan = tmr_amd._lib.mask_boxes_plan(h=h, w=w, H=H, W=W)
+    assert plan == want, f"the band rule moved: {shape} now runs {plan}, this test was written for {want}"
+    return plan
+
+
+def both_modes(masks, size, seed):
+    """check_against_ref in forward and in scaled mode; all three outputs bit-equal."""
+    lg, iou = rows_for(np.random.default_rng(seed), masks.shape[0])
+    got = check_against_ref(masks, size, lg, iou)
+    check_against_ref(masks, size, lg, iou, np.array([1.25, 0.5, 3.0, 2.0], f32))
+    return got
+
+
+@pytest.mark.parametrize("shape,stride", refine_ref.RAMP_SHAPES,
+                         ids=["x".join(map(str, s)) for s, _ in refine_ref.RAMP_SHAPES])
+def test_ramp_masks_equal_restatement(shape, stride):
+    """Masks whose box rests on the last bits of v (refine_ref.ramp_masks; no
+    margin filter): bit-equality with the restatement holds only if every
+    operation of the rule is rounded on its own, in its order -- the host test
+    shows that one fused multiply-add per expression moves at least 10 of
+    these boxes at each shape.  The last three shapes run the reduced bands."""
+    h, w, H, W = shape
+    if shape in REDUCED_BANDS:
+        plan = assert_plan(shape, REDUCED_BANDS[shape])
+        assert plan[0] < 16
+    else:
+        plan = tmr_amd._lib.mask_boxes_plan(h=h, w=w, H=H, W=W)
+        assert plan[0] == 16
+    masks = refine_ref.ramp_masks(h, w, H, W, stride)
+    both_modes(masks, (H, W), 11 + sum(shape))
+    ib = refine_ref.int_boxes(masks, (H, W))
+    assert len({tuple(b) for b in ib}) > len(masks) // 4  # the boxes move with the ramp's zero
+    print(f"ramp masks {shape}: plan (band rows, cap rows, bands) {plan}, {len(masks)} masks bit-equal")
+
+
+def single_pixel_case(shape, want_plan, spots, span, span_box, seed):
+    """One positive pixel per mask at an identity size ratio, plus one mask
+    holding the `span` pixels: literal boxes, then the kernel against them."""
+    h, w, H, W = shape
+    assert (h, w) == (H, W)
+    assert_plan(shape, want_plan)
+    masks = np.full((len(spots) + 1, H, W), -10.0, f32)
+    for n, (y, x) in enumerate(spots):
+        masks[n, y, x] = 1.0
+    for y, x in span:
+        masks[-1, y, x] = 1.0
+    lg, iou = rows_for(np.random.default_rng(seed), masks.shape[0])
+    got = check_against_ref(masks, (H, W), lg, iou)
+    ib = refine_ref.int_boxes(masks, (H, W))
+    for n, (y, x) in enumerate(spots):
+        assert tuple(ib[n]) == (x, y, x, y)
+    assert tuple(ib[-1]) == span_box
+    assert same(got[1].cpu().numpy(), ib.astype(f32) / np.array([W, H, W, H], f32))
+    check_against_ref(masks, (H, W), lg, iou, np.array([0.5, 2.0, 1.0, 3.0], f32))
+
+
+def test_single_pixels_one_row_bands():
+    """(5, 2100) at an identity ratio: 1-row bands, 3 rows staged at most.
+    Corners, either side of the block's 256-column stride and of column 2048."""
+    W = 2100
+    spots = [(0, 0), (0, W - 1), (4, 0), (4, W - 1), (2, 255), (2, 256), (1, 2047), (3, 2048), (4, 2047), (0, 2048)]
+    single_pixel_case((5, W, 5, W), (1, 3, 5), spots, [(1, 255), (3, 2048), (2, 256)], (255, 1, 2048, 3), 21)
+
+
+def test_single_pixels_eleven_row_bands():
+    """(20, 600) at an identity ratio: 11-row bands, the last one 9 rows.
+    Either side of the band edge between rows 10 and 11, and in the last band."""
+    W = 600
+    spots = [(0, 0), (0, W - 1), (10, 5), (11, 5), (10, W - 1), (11, 0), (10, 255), (11, 256), (12, 255), (15, 256),
+             (19, 0), (19, W - 1), (18, 300)]
+    single_pixel_case((20, W, 20, W), (11, 13, 2), spots, [(10, 255), (11, 256), (19, 10)], (10, 10, 256, 19), 22)
+
+
+def many_masks(N):
+    """N masks 3 x 3 (for a 6 x 8 image): unfiltered blobs, then corner_masks (the last one non-empty)."""
+    return np.concatenate([refine_ref.blob_masks(np.random.default_rng(1000 + N), N - 6, 3, 3), corner_masks(3, 3)])
+
+
+@pytest.mark.parametrize("N", [256, 257, 600])
+def test_more_masks_than_one_init_block(N):
+    """The init and epilogue kernels handle 256 masks per block: N = 256 fills
+    one, 257 and 600 run a second and a third, with a non-empty last mask."""
+    masks = many_masks(N)
+    assert masks.shape == (N, 3, 3)
+    ib = refine_ref.int_boxes(masks, (6, 8))
+    assert tuple(ib[-1]) != (0, 0, 0, 0) and ib[-1][2] == 7 and ib[-1][3] == 5
+    if N > 256:
+        assert (ib[256:, 2] > 0).any()  # real boxes past the first block
+    got = both_modes(masks, (6, 8), N)
+    assert tuple(got[1].shape) == (N, 4)
+    print(f"N = {N}: bit-equal")
+
+
+@pytest.mark.parametrize("shape", [(16, 16, 64, 64), (12, 9, 7, 4)], ids=lambda s: "x".join(map(str, s)))
+def test_unfiltered_blobs_equal_restatement(shape):
+    """blob_masks as drawn, without the margin_ok re-draw of the tests above:
+    bit-equality needs no margin."""
+    h, w, H, W = shape
+    masks = refine_ref.blob_masks(np.random.default_rng(300 + sum(shape)), 200, h, w)
+    both_modes(masks, (H, W), 31 + sum(shape))
+
+
 @pytest.mark.parametrize("bad", [np.nan, np.inf])
 def test_non_finite_corner(bad):
     """A NaN corner is evaluated literally (its pixels are not positive, its
@@ -323,6 +433,36 @@ def test_refine_route_under_guarded_allocator(golden):
     output element is left unwritten, nothing reads the uninitialised work
     buffer) and no guard byte around any allocation is written."""
     flow = _refine_flow(golden("refine"))
+    with ga.context(None, DEV) as a:
+        plain = flow(a)
+    for poison in (ga.POISON_ZERO, ga.POISON_FF):  # zero first
+        with ga.GuardedAlloc(poison, DEV) as a:
+            out = flow(a)
+            assert len(a.records) > 0
+            a.check()
+        _bits(plain, out, f"poison {poison:#x}")
+
+
+def test_reduced_bands_and_many_masks_under_guarded_allocator():
+    """A reduced-band geometry (12-row bands, ramp masks) and N = 600 (three
+    init / epilogue blocks) under the guarded allocator: same bits unpatched,
+    zero- and 0xFF-poisoned, no guard byte written."""
+    shape = (200, 100, 30, 45)
+    assert_plan(shape, REDUCED_BANDS[shape])
+    ramps = refine_ref.ramp_masks(*shape)
+    many = many_masks(600)
+    scaler = np.array([2, 0.5, 1, 3], f32)
+
+    def flow(a):
+        place = lambda x: a.place(np.ascontiguousarray(x))  # noqa: E731
+        out = {}
+        for key, masks, size in (("ramps", ramps, shape[2:]), ("many", many, (6, 8))):
+            lg, iou = rows_for(np.random.default_rng(8), masks.shape[0])
+            out[key] = [t.cpu().numpy() for t in check_against_ref(masks, size, lg, iou, place=place)]
+            out[key + "_scaled"] = [t.cpu().numpy() for t in check_against_ref(masks, size, lg, iou, scaler,
+                                                                               place=place)]
+        return out
+
     with ga.context(None, DEV) as a:
         plain = flow(a)
     for poison in (ga.POISON_ZERO, ga.POISON_FF):  # zero first

@@ -94,6 +94,58 @@ def test_empty_exemplar_mask_has_no_scaler():
     assert refine_ref.exemplar_scaler(-np.ones((4, 5), np.float32), (9, 11), [0.1, 0.1, 0.5, 0.5]) is None
 
 
+def test_ramp_masks_tell_a_contracted_build_apart():
+    """The condition that makes the GPU comparison on the ramp masks
+    meaningful: at each ramp shape at least 10 masks change their integer box
+    between the rule (every operation rounded on its own) and the same
+    expressions with one fused multiply-add each.  Measured: 123 of 248, 53 of
+    112, 111 of 296, 24 of 142, 12 of 106."""
+    counts = {(16, 16, 64, 64): 248, (7, 11, 23, 37): 112, (30, 700, 37, 900): 296, (200, 100, 30, 45): 142,
+              (3, 4096, 7, 50): 106}
+    for shape, stride in refine_ref.RAMP_SHAPES:
+        h, w, H, W = shape
+        masks = refine_ref.ramp_masks(h, w, H, W, stride)
+        assert masks.shape == (counts[shape], h, w) and masks.dtype == np.float32
+        assert same(masks[1], -masks[0])
+        rule = refine_ref.int_boxes(masks, (H, W))
+        fused = refine_ref.int_boxes(masks, (H, W), refine_ref.upsample_contracted)
+        changed = int((rule != fused).any(1).sum())
+        print(f"ramp masks {shape}: {changed} of {len(masks)} boxes change under contraction")
+        assert changed >= 10, (shape, changed)
+        assert not refine_ref.margin_ok(masks, (H, W))  # these are the masks the margin filter removes
+
+
+def test_mask_boxes_plan_no_gpu():
+    """tmr_mask_boxes_plan: the band rule on the host (band rows, staged-row cap, bands per mask)."""
+    plan = _lib.mask_boxes_plan
+    assert plan(h=16, w=16, H=64, W=64) == (16, 512, 4)
+    assert plan(h=40, w=300, H=40, W=300) == (16, 27, 3)  # the largest full-height band of the suite: 18 rows staged
+    assert plan(h=30, w=700, H=37, W=900) == (11, 11, 4)  # staged rows at their cap
+    assert plan(h=200, w=100, H=30, W=45) == (12, 81, 3)
+    assert plan(h=3, w=4096, H=7, W=50) == (1, 2, 7)  # the widest mask
+    assert plan(h=5, w=2100, H=5, W=2100) == (1, 3, 5)
+    assert plan(h=20, w=600, H=20, W=600) == (11, 13, 2)
+    L = tmr_amd.load()
+    out = [ctypes.c_int32(7) for _ in range(3)]
+
+    def rc(**kw):
+        f = dict(N=1, h=4, w=4, H=8, W=8, mode=0)
+        f.update(kw)
+        return L.tmr_mask_boxes_plan(ctypes.byref(_lib._fill(_lib.MaskBoxesArgs, "tmr_mask_boxes_args_t", f)),
+                                     *(ctypes.byref(o) for o in out))
+
+    assert rc(w=4097) == -1 and [o.value for o in out] == [0, 0, 0]
+    assert rc() == -1  # null buffers with N > 0, as tmr_mask_boxes
+    assert rc(N=0) == 0 and [o.value for o in out] == [16, 2048, 1]
+    assert L.tmr_mask_boxes_plan(None, None, None, None) == -1
+    try:
+        plan(h=0, w=4, H=8, W=8)
+    except tmr_amd.TMRError:
+        pass
+    else:
+        raise AssertionError("an invalid shape must raise TMRError")
+
+
 def header_symbols():
     txt = open(os.path.join(REPO, "include", "tmr_refine.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
@@ -102,7 +154,7 @@ def header_symbols():
 
 def test_extension_symbols():
     syms = header_symbols()
-    assert syms == ["tmr_mask_boxes"]
+    assert syms == ["tmr_mask_boxes", "tmr_mask_boxes_plan"]
     assert set(syms) == set(_lib.EXT_SIGNATURES), "ctypes table out of sync with tmr_refine.h"
     assert not set(syms) & set(_lib.SIGNATURES), "the extension stays outside the core ABI table"
     lib = ctypes.CDLL(_lib.LIB_PATH)
