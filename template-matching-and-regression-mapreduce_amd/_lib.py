@@ -158,6 +158,31 @@ REFINE_FORWARD, REFINE_SCALED = 0, 1  # tmr_mask_boxes_args_t.mode
 MASK_BOXES_WORK_PER_MASK = 16  # TMR_MASK_BOXES_WORK_BYTES(N) = 16 * N
 
 
+class CocoMatchArgs(ctypes.Structure):
+    """tmr_coco_match_args_t (include/tmr_coco.h)."""
+    _fields_ = [("det_off", _P), ("det_box", _P), ("det_area", _P), ("gt_off", _P), ("gt_box", _P),
+                ("gt_area", _P), ("gt_crowd", _P), ("area_rng", _P), ("iou_thr", _P), ("dt_match", _P),
+                ("dt_ignore", _P), ("gt_ignore", _P), ("gt_match", _P), ("sum_d", _L), ("sum_g", _L),
+                ("I", ctypes.c_int32), ("A", ctypes.c_int32), ("T", ctypes.c_int32), ("max_d", ctypes.c_int32),
+                ("max_g", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class CocoMatchPlan(ctypes.Structure):
+    """tmr_coco_match_plan_t (include/tmr_coco.h)."""
+    _fields_ = [("variant", ctypes.c_int32), ("tile_cap", ctypes.c_int32), ("list_cap", ctypes.c_int32),
+                ("threads", ctypes.c_int32), ("lds_bytes", ctypes.c_int32), ("blocks", ctypes.c_int32)]
+
+
+# the COCO AP matching extension (include/tmr_coco.h): same libtmr.so, outside the core ABI as well
+COCO_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_coco.h")
+COCO_SIGNATURES = {
+    "tmr_coco_match": (_I, [ctypes.POINTER(CocoMatchArgs), _P]),
+    "tmr_coco_match_plan": (_I, [ctypes.POINTER(CocoMatchArgs), ctypes.POINTER(CocoMatchPlan)]),
+}
+COCO_VARIANTS = {0: "lds", 1: "global"}  # TMR_COCO_VARIANT_*
+COCO_T_MAX, COCO_D_MAX, COCO_G_MAX = 16, 4096, 65536
+
+
 class TMRError(RuntimeError):
     pass
 
@@ -175,7 +200,8 @@ def load() -> ctypes.CDLL:
                 f"libtmr.so not found at {LIB_PATH}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
+                                  + list(COCO_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -290,6 +316,31 @@ def mask_boxes_plan(**fields):
     check(load().tmr_mask_boxes_plan(ctypes.byref(_fill(MaskBoxesArgs, "tmr_mask_boxes_args_t", fields)),
                                      *(ctypes.byref(o) for o in out)), "tmr_mask_boxes_plan")
     return tuple(o.value for o in out)
+
+
+def coco_match(stream_=None, **fields) -> None:
+    """tmr_coco_match(&args, stream) (include/tmr_coco.h)."""
+    check(load().tmr_coco_match(ctypes.byref(_fill(CocoMatchArgs, "tmr_coco_match_args_t", fields)), stream_),
+          "tmr_coco_match")
+
+
+def coco_match_plan_rc(**fields):
+    """tmr_coco_match_plan(&args, &plan) -> (return code, plan dict or None); host only."""
+    plan = CocoMatchPlan()
+    rc = load().tmr_coco_match_plan(ctypes.byref(_fill(CocoMatchArgs, "tmr_coco_match_args_t", fields)),
+                                    ctypes.byref(plan))
+    if rc != 0:
+        return rc, None
+    out = {n: getattr(plan, n) for n, _ in CocoMatchPlan._fields_}
+    out["variant"] = COCO_VARIANTS[plan.variant]
+    return rc, out
+
+
+def coco_match_plan(**fields):
+    """coco_match_plan_rc's plan; raises TMRError where tmr_coco_match would refuse the call."""
+    rc, plan = coco_match_plan_rc(**fields)
+    check(rc, "tmr_coco_match_plan")
+    return plan
 
 
 def require_gpu(t: torch.Tensor, name: str = "input") -> None:
