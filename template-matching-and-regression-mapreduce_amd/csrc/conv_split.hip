@@ -878,6 +878,20 @@ constexpr int PTW = NWAVES / WNS;  // channel tiles per pass
 static_assert(PT == 64 && 4 * PP == NTHREADS, "points block: one store lane per head and point");
 static_assert(WNS == 2 && NWAVES == 2 * P, "points block: a wave per 64-channel half; gathers dealt by (piece, half)");
 
+// This lane's index, formed where it is called: the points kernel's prologue
+// and epilogues take their lane indices from here, so that none of them (nor
+// anything derived from them) holds a lane register across a K loop.
+__device__ __forceinline__ int lane_now() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+// v of lane src (0..63)
+__device__ __forceinline__ int lane_read(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+__device__ __forceinline__ float lane_read(float v, int src) {
+    return __builtin_bit_cast(float, lane_read(__builtin_bit_cast(int, v), src));
+}
+
 struct PArgs {
     SArgs s;
     const float *head_bias;
@@ -923,13 +937,16 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         const int64_t ti = 2 * (int64_t)blockIdx.x + hh;
         const bool have = ti < pa.ntiles;
         const int32_t *tl = pa.tiles + 3 * (have ? ti : ti - hh);
-        tu[hh] = min(max(tl[0], 0), a.U - 1);
-        tfirst[hh] = min(max(tl[1], 0), HW - 1);
-        tcnt[hh] = have ? min(max(tl[2], 0), PT) : 0;
-        timg[hh] = a.unit_image ? a.unit_image[tu[hh]] : tu[hh];
-        sxw[hh] = split_sxw<PREC>(a, tu[hh]);
+        // (block-uniform values, pinned to scalar registers: none of them
+        // may take a lane register across the K loop)
+        tu[hh] = __builtin_amdgcn_readfirstlane(min(max(tl[0], 0), a.U - 1));
+        tfirst[hh] = __builtin_amdgcn_readfirstlane(min(max(tl[1], 0), HW - 1));
+        tcnt[hh] = __builtin_amdgcn_readfirstlane(have ? min(max(tl[2], 0), PT) : 0);
+        timg[hh] = __builtin_amdgcn_readfirstlane(a.unit_image ? a.unit_image[tu[hh]] : tu[hh]);
+        sxw[hh] = __builtin_bit_cast(
+            float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, split_sxw<PREC>(a, tu[hh]))));
     }
-    const int NC = a.NC0 + a.NC1;
+    const int NC = a.NC0 + a.NC1, NHC = NC * HALVES;
     // point p of a host tile: its pixel (a point past the tile's count repeats
     // a legal candidate row and is never stored; a pixel index is clamped into
     // the map, so no gather leaves the padded plane)
@@ -947,10 +964,13 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     // turns a stray read into zeros instead of a fault
     const uint32_t cstride = (uint32_t)a.Hp * a.Wp * XREC;
     const int h0 = a.NC0 * HALVES, h1 = a.NC1 * HALVES;
-    const __amdgpu_buffer_rsrc_t xr0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(h0 ? a.x0 + (size_t)gimg * h0 * cstride : a.x1), (short)0, h0 * cstride, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xr1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(h1 ? a.x1 + (size_t)gu * h1 * cstride : a.x0), (short)0, h1 * cstride, 0x00020000);
+    auto uniform_ptr = [](const char *p) {  // (a 64-bit multiply-add is lane arithmetic: back to scalars)
+        const uint64_t v = (uint64_t)p;
+        return (const char *)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+                              (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
+    };
+    const char *xb0 = uniform_ptr(h0 ? a.x0 + (size_t)gimg * h0 * cstride : a.x1);  // h0 * cstride records
+    const char *xb1 = uniform_ptr(h1 ? a.x1 + (size_t)gu * h1 * cstride : a.x0);    // h1 * cstride records
     const uint32_t tapstride = (uint32_t)NC * a.Npad * WREC;
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
         (void *)a.wp, (short)0, T * tapstride, 0x00020000);
@@ -967,29 +987,44 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     // 6.35 ms; 5.0 ms with the second K loop's gathers left out, 3.95 ms with
     // none, 4.3 ms with every lane reading one pixel): the candidates touch
     // most 128-B lines of the packed planes for 48 B each, once per K loop.
+    // (0.9 ms of those 6.35 were not the gather: that build reloaded spilled
+    // accumulators at the top of each chunk, each reload with a vmcnt(0)
+    // directly behind the gather's issue.  The kernel now holds its K loop,
+    // prologue and epilogues in registers, 0 spills in every precision
+    // (profiles/points_kloop/resources.json): 6.24 -> 5.34 ms on one box.)
     // Measured and dropped: a wave's gather instructions spread over the
     // half-chunk's stages (7.7 ms: vmcnt counts in issue order, so every
     // stage's wait for its weights then waits for a gather instruction), and
     // waves 4-7 alone gathering, so that a stalled wave's SIMD partner keeps
     // the matrix pipe (6.3 ms: no change).
+    // (lane l reads the pixel of point l once; a gather lane takes its point's from that lane)
+    const int gpix0 = pixel(gu, gfirst, gcnt, lane);
     uint32_t goff[KS];
 #pragma unroll
     for (int i = 0; i < KS; ++i) {
         const int g = 64 * i + lane;
-        const int pix = pixel(gu, gfirst, gcnt, g / KS), y = pix / a.W;
+        const int pix = lane_read(gpix0, g / KS), y = pix / a.W;
         goff[i] = (uint32_t)(y * a.Wp + (pix - y * a.W) + g % KS) * 16;
     }
     const uint32_t qstride = (uint32_t)a.Hp * a.Wp * 16;
-    auto gather = [&](int hc) {
-        const bool s0 = hc < h0;
-        const uint32_t hs_ = (uint32_t)(s0 ? hc : hc - h0) * cstride + wt * qstride;
+    // The K loop issues it without a branch (one basic block: the register
+    // allocator then keeps every accumulator in place, and a stage's f * 256
+    // stays an instruction offset): past the last half-chunk, `live` false,
+    // the instructions address the last half-chunk through a descriptor of
+    // zero records, so the range check drops every read, and they target the
+    // buffer that is not read again before the loop's closing barrier.
+    auto gather = [&](int hc, bool live = true) {
+        const int hcl = min(hc, NHC - 1);
+        const bool s0 = hcl < h0;
+        const uint32_t hs_ = (uint32_t)(s0 ? hcl : hcl - h0) * cstride + wt * qstride;
+        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(s0 ? xb0 : xb1), (short)0, live ? (s0 ? h0 : h1) * cstride : 0, 0x00020000);
 #pragma unroll
         for (int ky = 0; ky < KS; ++ky)
 #pragma unroll
             for (int i = 0; i < KS; ++i)
-                buffer_lds16(s0 ? xr0 : xr1,
-                             (lds_ptr_t)(Bs + (hc & 1) * BB + (((ky * P + wt) * PP + wh * PT) * KS + 64 * i) * 16), goff[i],
-                             hs_ + (uint32_t)(ky * a.Wp) * 16);
+                buffer_lds16(xr, (lds_ptr_t)(Bs + (hc & 1) * BB + (((ky * P + wt) * PP + wh * PT) * KS + 64 * i) * 16),
+                             goff[i], hs_ + (uint32_t)(ky * a.Wp) * 16);
     };
     // this lane's slot of a (ky, kx = 0, column group 0) fragment: a point's
     // slots are KS * 16 B apart, 12 banks: the 16 lanes of a ds_read_b128
@@ -1007,44 +1042,81 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         const int wtile = pass * PTW + wt;
         const bool active = wtile < a.NTW;
         const int nt = a.NT0 + (active ? wtile : 0);
-        const uint32_t aoff = (uint32_t)kg * a.Npad * 16 + ((uint32_t)nt * BM + wh * (BM / 2) + l16) * 16;
+        const int lp = lane_now(), l16p = lp & 15, kgp = lp >> 4;
+        uint32_t aoff = (uint32_t)kgp * a.Npad * 16 + ((uint32_t)nt * BM + wh * (BM / 2) + l16p) * 16;
         // (pass 1: buffer 0 was last read before the K loop's closing barrier;
         // the odd waves' sums of pass 0 sit in buffer 1)
         gather(0);
 
         f32x4 acc[NF][PCG];
         if (a.acc_init) {  // tiled (host-checked): the dense kernel's element of slab / tile / wave / lane
-            const bool i16 = a.flags & TMR_SPLIT_INIT_BF16;
-#pragma unroll
-            for (int j = 0; j < PCG; ++j) {
-                constexpr int HJ = PCG / 2;  // column groups per host tile
+            constexpr int HJ = PCG / 2;  // column groups per host tile
+            // (formed per pass: hoisted out of the pass loop, the pixels, the
+            // flags' tests and the reciprocal of W would cross the K loop)
+            int Wd = a.W, fl = a.flags;
+            asm volatile("" : "+s"(Wd), "+s"(fl));
+            // lane l reads the pixel of point l of each host tile once; a
+            // column's lane takes it from there
+            const int ppix[2] = {pixel(tu[0], tfirst[0], tcnt[0], lp), pixel(tu[1], tfirst[1], tcnt[1], lp)};
+            // 16-B group index of column group j's element (wave wpix * WNS + wh, in 0): + f * 8 groups of 64
+            auto group4 = [&](int j) {
                 const int hh = j / HJ;
-                const int pix = pixel(tu[hh], tfirst[hh], tcnt[hh], (j % HJ) * 16 + l16);
-                const int py = pix / a.W, px = pix - py * a.W;
-                const float sx = sxw[hh];
-                const int islab = (a.flags & TMR_SPLIT_INIT_BCAST) ? 0 : timg[hh];
+                const int pix = lane_read(ppix[hh], (j % HJ) * 16 + l16p);
+                const int py = pix / Wd, px = pix - py * Wd;
+                const int islab = (fl & TMR_SPLIT_INIT_BCAST) ? 0 : timg[hh];
                 const int mt = (py / TH) * a.TXN + px / TW;
                 const int wpix = (py % TH) >> 2, jp = ((py & 3) << 1) | ((px % TW) >> 4);
-                // 16-B group index of (wave wpix * WNS + wh, in 0): + f * 8 groups of 64
-                const size_t g4 = (((((size_t)islab * a.NT + nt) * a.MT + mt) * NWAVES + wpix * WNS + wh) * ACCW) / 4 +
-                                  jp * 64 + kg * 16 + (px & 15);
-                if (i16) {
-                    const b4 *ai = reinterpret_cast<const b4 *>(a.acc_init) + g4;
+                // = (((((size_t)islab * a.NT + nt) * a.MT + mt) * NWAVES + wpix * WNS + wh) * ACCW) / 4 + jp * 64
+                // + kgp * 16 + (px & 15), the lane's part put together from 32-bit halves (H W < 2^29: row <
+                // 2^23; in < ACCW / 4): a 64-bit lane sum takes a zero high half that would cross the K loop
+                static_assert(ACCW / 4 == 1 << 11 && 8 * 64 <= ACCW / 4, "the shifts below");
+                const uint32_t row = (uint32_t)(mt * NWAVES + wpix * WNS + wh), in = jp * 64 + kgp * 16 + (px & 15);
+                typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+                u2 lh = {row << 11 | in, row >> 21};
+                asm volatile("" : "+v"(lh));  // (opaque, or the sum is taken apart again)
+                return ((size_t)islab * a.NT + nt) * a.MT * NWAVES * (ACCW / 4) + __builtin_bit_cast(uint64_t, lh);
+            };
+            // one column group at a time, pinned: its address arithmetic is
+            // dead before the next group's starts (unpinned, the scheduler
+            // hoists the eight groups' together and spills them); the loads
+            // all fly before the first is scaled
+            if (fl & TMR_SPLIT_INIT_BF16) {  // (the raw pairs wait in the accumulator's first two registers)
 #pragma unroll
-                    for (int f = 0; f < NF; ++f)
-                        acc[f][j] = __builtin_convertvector(ai[f * 8 * 64], f32x4) * sx;
-                } else {
-                    const f32x4 *ai = reinterpret_cast<const f32x4 *>(a.acc_init) + g4;
+                for (int j = 0; j < PCG; ++j) {
+                    const b4 *ai = reinterpret_cast<const b4 *>(a.acc_init) + group4(j);
 #pragma unroll
-                    for (int f = 0; f < NF; ++f)
-                        acc[f][j] = ai[f * 8 * 64] * sx;
+                    for (int f = 0; f < NF; ++f) {
+                        const f2 raw = __builtin_bit_cast(f2, ai[f * 8 * 64]);
+                        acc[f][j] = (f32x4){raw.x, raw.y, 0.0f, 0.0f};
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
                 }
+#pragma unroll
+                for (int j = 0; j < PCG; ++j)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f)
+                        acc[f][j] = __builtin_convertvector(__builtin_bit_cast(b4, (f2){acc[f][j][0], acc[f][j][1]}),
+                                                            f32x4) * sxw[j / HJ];
+            } else {
+#pragma unroll
+                for (int j = 0; j < PCG; ++j) {
+                    const f32x4 *ai = reinterpret_cast<const f32x4 *>(a.acc_init) + group4(j);
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) acc[f][j] = ai[f * 8 * 64];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int j = 0; j < PCG; ++j)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) acc[f][j] = acc[f][j] * sxw[j / HJ];
             }
         } else {
+            float zf = 0.0f;  // (a zero of this pass, not a zero quad held from pass to pass)
+            asm volatile("" : "+v"(zf));
 #pragma unroll
             for (int f = 0; f < NF; ++f)
 #pragma unroll
-                for (int j = 0; j < PCG; ++j) acc[f][j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+                for (int j = 0; j < PCG; ++j) acc[f][j] = (f32x4){zf, zf, zf, zf};
         }
 
         // stage s of a chunk: F16X3 s < 2T: hi half-chunk, tap s / 2, term s % 2
@@ -1061,13 +1133,14 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         constexpr int AR = 3;
         static_assert(NS % AR == 0 && NS >= AR, "weight ring");
         V ar[AR][NF];
+        uint32_t ts = tapstride, npl = (uint32_t)a.Npad * 16;  // bytes per tap, per weight plane of a chunk
         auto load_stage = [&](int c, int s) {  // (past the end: a harmless re-read of the last chunk)
             if (s >= NS) {
                 s -= NS;
                 c = c + 1 < NC ? c + 1 : c;
             }
-            const uint32_t as = (uint32_t)st_tap(s) * tapstride + (uint32_t)c * a.Npad * WREC +
-                                (uint32_t)st_term(s) * 4 * a.Npad * 16;
+            const uint32_t as = (uint32_t)st_tap(s) * ts + (uint32_t)c * npl * (WREC / 16) +
+                                (uint32_t)st_term(s) * 4 * npl;
 #pragma unroll
             for (int f = 0; f < NF; ++f) ar[s % AR][f] = buffer_load16<V>(wr, aoff + f * 256, as);
         };
@@ -1075,9 +1148,22 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         for (int s = 0; s < AR - 1; ++s) load_stage(0, s);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        V bc[PCG];
-        const int NHC = NC * HALVES;
+        // B fragments: a rolling window of BW column groups.  One-term: every
+        // stage takes a new tap, so the window costs no LDS read and frees 16
+        // registers; F16X3 holds the whole stage, which its wl stage reuses
+        constexpr int BW = HALVES == 2 ? PCG : PCG / 2;
+        static_assert(PCG % BW == 0, "a group's slot is j % BW in every stage");
+        V bc[BW];
         for (int c = 0; c < NC; ++c) {
+            // one voffset register for a stage's NF fragments: opaque per
+            // chunk, so that aoff + f * 256 is formed beside its load and
+            // f * 256 folds into the instruction's offset (hoisted out of the
+            // loop, the four sums hold four registers)
+            asm volatile("" : "+v"(aoff));
+            // likewise the two strides of a stage's soffset: the NS stage
+            // offsets are two scalar multiplies each, not NS scalar registers
+            // held (and spilled to lanes) across the loop
+            asm volatile("" : "+s"(ts), "+s"(npl));
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int hc = c * HALVES + st_part(s);
@@ -1089,22 +1175,26 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
                 // order) covers a gather issued less than AR - 1 stages before
                 load_stage(c, s + AR - 1);
                 if (st_first(s)) {
-                    if (hc + 1 < NHC) gather(hc + 1);
+                    gather(hc + 1, hc + 1 < NHC);
 #pragma unroll
-                    for (int j = 0; j < PCG; ++j) bc[j] = bfrag(hc, st_tap(s), j);
+                    for (int j = 0; j < BW; ++j) bc[j] = bfrag(hc, st_tap(s), j);
                 }
                 // A column group's B fragment is dead after its NF MFMAs: the
-                // next stage's, where that stage takes a new tap of the same
-                // half-chunk, is read into its place (a half-chunk's first B
-                // waits for its barrier, above)
-                const bool nextb = s + 1 < NS && st_newb(s + 1) && !st_first(s + 1);
+                // fragment BW groups on in the half-chunk's stream (this
+                // stage's group j + BW, or the next stage's group j + BW - PCG)
+                // is read into its place; with the whole stage held (BW = PCG)
+                // a stage on the same tap reads nothing (a half-chunk's first
+                // B waits for its barrier, above)
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < PCG; ++j) {
 #pragma unroll
-                    for (int f = 0; f < NF; ++f) acc[f][j] = mma(ar[s % AR][f], bc[j], acc[f][j]);
-                    if (nextb) {
-                        bc[j] = bfrag(hc, st_tap(s + 1), j);
+                    for (int f = 0; f < NF; ++f) acc[f][j] = mma(ar[s % AR][f], bc[j % BW], acc[f][j]);
+                    if (j + BW < PCG) {
+                        bc[j % BW] = bfrag(hc, st_tap(s), j + BW);
+                        __builtin_amdgcn_sched_barrier(0);
+                    } else if (!st_last(s) && (BW < PCG || st_newb(s + 1))) {
+                        bc[j % BW] = bfrag(hc, st_tap(s + 1), j + BW - PCG);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -1121,6 +1211,11 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
             }
         }
 
+        // (the epilogue's lane indices are formed after the loop: held across
+        // it, they and what is derived from them take lane registers there)
+        const int le = lane_now(), kge = le >> 4, l16e = le & 15;
+        float se[2] = {sxw[0], sxw[1]};  // (likewise the reciprocals below)
+        asm volatile("" : "+s"(se[0]), "+s"(se[1]));
         // heads of this half tile: lane group kg holds rows n = 64 wh + 16 f +
         // 4 kg + r; column groups (2q, 2q + 1) lie in one host tile
         f2 hs[PCG / 2][NHEAD];
@@ -1128,26 +1223,44 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         for (int q = 0; q < PCG / 2; ++q)
 #pragma unroll
             for (int k = 0; k < NHEAD; ++k) hs[q][k] = (f2){0.0f, 0.0f};
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
+        // the bias and head weights of fragment f + 1 load while fragment f
+        // is summed, pinned (unpinned, the scheduler hoists the 96 loads of
+        // the four fragments above the sums and spills accumulators)
+        float bvs[2][4], hws[2][4][NHEAD];
+        auto load_hw = [&](int f) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int n = nt * BM + wh * (BM / 2) + f * 16 + 4 * kg + r;
-                const float bv = n < a.N ? a.bias[n] : 0.0f;
+                const int n = nt * BM + wh * (BM / 2) + f * 16 + 4 * kge + r;
+                const float bl = a.bias[min(n, a.N - 1)];  // (no branch: the epilogue stays one block)
+                bvs[f & 1][r] = n < a.N ? bl : 0.0f;
+#pragma unroll
+                for (int k = 0; k < NHEAD; ++k) hws[f & 1][r][k] = a.headw[(size_t)n * NHEAD + k];
+            }
+        };
+        load_hw(0);
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            if (f + 1 < NF) load_hw(f + 1);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float bv = bvs[f & 1][r];
                 const f2 bn2 = {bv, bv};
                 f2 hw2[NHEAD];
 #pragma unroll
                 for (int k = 0; k < NHEAD; ++k) {
-                    const float h = a.headw[(size_t)n * NHEAD + k];
+                    const float h = hws[f & 1][r][k];
                     hw2[k] = (f2){h, h};
                 }
 #pragma unroll
                 for (int q = 0; q < PCG / 2; ++q) {
-                    const float inv = 1.0f / sxw[q / (PCG / 4)];
+                    const float inv = 1.0f / se[q / (PCG / 4)];
                     head_fma(head_act((f2){acc[f][2 * q][r], acc[f][2 * q + 1][r]}, (f2){inv, inv}, bn2, a.leaky), hw2,
                              hs[q]);
                 }
             }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // over the lane groups, (x0 + x1) + (x2 + x3)
         float z[PCG / 2][4][2];
 #pragma unroll
@@ -1157,29 +1270,29 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const float x = hs[q][k][e];
-                    const float y = x + __shfl_xor(x, 16);
-                    z[q][k][e] = y + __shfl_xor(y, 32);
+                    const float y = x + lane_read(x, le ^ 16);
+                    z[q][k][e] = y + lane_read(y, le ^ 32);
                 }
         // then the two halves, z[0] + z[1]: the odd wave's through LDS (the
         // K loop's closing barrier freed the B buffers; buffer 1 is next
         // written by the gather a pass issues after its opening barrier)
-        if (wh == 1 && kg == 0 && active) {
+        if (wh == 1 && kge == 0 && active) {
 #pragma unroll
             for (int q = 0; q < PCG / 2; ++q)
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
 #pragma unroll
-                    for (int e = 0; e < 2; ++e) xch[wt][k][(2 * q + e) * 16 + l16] = z[q][k][e];
+                    for (int e = 0; e < 2; ++e) xch[wt][k][(2 * q + e) * 16 + l16e] = z[q][k][e];
         }
         __syncthreads();
-        if (wh == 0 && kg == 0 && active) {
+        if (wh == 0 && kge == 0 && active) {
 #pragma unroll
             for (int q = 0; q < PCG / 2; ++q)
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
-                        const int p = (2 * q + e) * 16 + l16;
+                        const int p = (2 * q + e) * 16 + l16e;
                         red[wtile][k][p] = z[q][k][e] + xch[wt][k][p];
                     }
         }
@@ -1187,7 +1300,8 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     __syncthreads();
     {
         // thread (head k, column p): wave w stores for the host tile of half w & 1
-        const int k = tid / PP, p = tid % PP, pl = p % PT;
+        const int te = wave * 64 + lane_now();  // (formed here, like the epilogue's indices)
+        const int k = te / PP, p = te % PP, pl = p % PT;
         if (pl < gcnt) {
             const int pix = pixel(gu, gfirst, gcnt, pl);
             float s = 0.0f;

@@ -514,9 +514,9 @@ class TMREngine:
     # when the candidates exceed BOX_POINTS_CROSSOVER of the pixels.
     box_at_peaks = "auto"  # "auto" | "always" | "never"
     # (dense decoder_b tiles' time per pixel) / (points launch's time per point), measured on one
-    # box at configs B-E (profiles/r08points/crossover.json, profiles/points_crossover.py): 3-term fp16
-    # 0.50-0.56, one term 0.48
-    BOX_POINTS_CROSSOVER = {"fp32": 0.50, "bf16": 0.47, "f16": 0.47}
+    # box at configs B-E (profiles/points_kloop/crossover.json, profiles/points_crossover.py): 3-term fp16
+    # 0.57-0.66, one term 0.48 (bf16; f16 has no bench config and keeps bf16's)
+    BOX_POINTS_CROSSOVER = {"fp32": 0.57, "bf16": 0.47, "f16": 0.47}
 
     def _box_tiles(self) -> int:
         """decoder_b's 128-channel tiles at the front of decoder_b || decoder_o."""
