@@ -18,6 +18,7 @@ from .tm_utils import (NMS, GT_map, Get_pred_boxes, Make_Template_size_predictio
                        NMS_process, adaptive_kernel_generater, calc_area, custom_shape_3x3_maxpool2d,
                        map_normalization)
 from .refine import SAM_box_refiner, mask_boxes  # noqa: F401
+from .maskhead import FusedMaskDecoder, mask_head, mask_head_weights  # noqa: F401
 from .coco_gpu import APMeter, CocoEvalGPU  # noqa: F401
 
 __all__ = [
@@ -26,6 +27,6 @@ __all__ = [
     "adaptive_kernel_generater", "Make_Template_size_predictions", "custom_shape_3x3_maxpool2d",
     "calc_area", "map_normalization", "TMREngine", "PathConfig",
     "GT_map", "SetCriterion_TM", "build_criterion", "gIoU_loss", "WeightedFocalLoss",
-    "SAM_box_refiner", "mask_boxes", "CocoEvalGPU", "APMeter",
+    "SAM_box_refiner", "mask_boxes", "FusedMaskDecoder", "mask_head", "mask_head_weights", "CocoEvalGPU", "APMeter",
     "TMRError", "build_backbone", "register_backbone", "unregister_backbone", "FeatureInput",
 ]

@@ -183,6 +183,31 @@ COCO_VARIANTS = {0: "lds", 1: "global"}  # TMR_COCO_VARIANT_*
 COCO_T_MAX, COCO_D_MAX, COCO_G_MAX = 16, 4096, 65536
 
 
+class MaskHeadArgs(ctypes.Structure):
+    """tmr_mask_head_args_t (include/tmr_maskhead.h)."""
+    _fields_ = [("src", _P), ("hyper", _P), ("w1", _P), ("w2", _P), ("wpack", _P), ("b1", _P), ("g", _P),
+                ("beta", _P), ("b2", _P), ("masks", _P), ("N", _L), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("C", ctypes.c_int32), ("eps", ctypes.c_float)]
+
+
+class MaskHeadPlan(ctypes.Structure):
+    """tmr_mask_head_plan_t (include/tmr_maskhead.h)."""
+    _fields_ = [("variant", ctypes.c_int32), ("tile_pixels", ctypes.c_int32), ("threads", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("tiles", ctypes.c_int32), ("blocks", ctypes.c_int32)]
+
+
+# the fused SAM mask head (include/tmr_maskhead.h): same libtmr.so, outside the core ABI as well
+MASKHEAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_maskhead.h")
+MASKHEAD_SIGNATURES = {
+    "tmr_mask_head_prep": (_I, [ctypes.POINTER(MaskHeadArgs), _P]),
+    "tmr_mask_head": (_I, [ctypes.POINTER(MaskHeadArgs), _P]),
+    "tmr_mask_head_plan": (_I, [ctypes.POINTER(MaskHeadArgs), ctypes.POINTER(MaskHeadPlan)]),
+}
+MASK_HEAD_VARIANTS = {0: "mfma128"}  # TMR_MASK_HEAD_VARIANT_*
+MASK_HEAD_WPACK_BYTES = 9 * 32768 + 64  # TMR_MASK_HEAD_WPACK_BYTES
+MASK_HEAD_DIM = 256  # the one transformer_dim the kernel is built for
+
+
 class TMRError(RuntimeError):
     pass
 
@@ -201,7 +226,7 @@ def load() -> ctypes.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
-                                  + list(COCO_SIGNATURES.items())):
+                                  + list(COCO_SIGNATURES.items()) + list(MASKHEAD_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -340,6 +365,39 @@ def coco_match_plan(**fields):
     """coco_match_plan_rc's plan; raises TMRError where tmr_coco_match would refuse the call."""
     rc, plan = coco_match_plan_rc(**fields)
     check(rc, "tmr_coco_match_plan")
+    return plan
+
+
+def mask_head_prep(stream_=None, **fields) -> None:
+    """tmr_mask_head_prep(&args, stream) (include/tmr_maskhead.h)."""
+    check(load().tmr_mask_head_prep(ctypes.byref(_fill(MaskHeadArgs, "tmr_mask_head_args_t", fields)), stream_),
+          "tmr_mask_head_prep")
+
+
+def mask_head(stream_=None, **fields) -> None:
+    """tmr_mask_head(&args, stream) (include/tmr_maskhead.h)."""
+    check(load().tmr_mask_head(ctypes.byref(_fill(MaskHeadArgs, "tmr_mask_head_args_t", fields)), stream_),
+          "tmr_mask_head")
+
+
+def mask_head_plan_rc(**fields):
+    """tmr_mask_head_plan(&args, &plan) -> (return code, plan dict or None); host only."""
+    plan = MaskHeadPlan()
+    fields.setdefault("C", MASK_HEAD_DIM)
+    rc = load().tmr_mask_head_plan(ctypes.byref(_fill(MaskHeadArgs, "tmr_mask_head_args_t", fields)),
+                                   ctypes.byref(plan))
+    if rc != 0:
+        return rc, None
+    out = {n: getattr(plan, n) for n, _ in MaskHeadPlan._fields_}
+    out["variant"] = MASK_HEAD_VARIANTS[plan.variant]
+    return rc, out
+
+
+def mask_head_plan(**fields):
+    """mask_head_plan_rc's plan; raises TMRError where tmr_mask_head would refuse the call.  With
+    N = 0 (the default) the geometry of (h, w) alone, whatever the pointers."""
+    rc, plan = mask_head_plan_rc(**fields)
+    check(rc, "tmr_mask_head_plan")
     return plan
 
 
