@@ -19,6 +19,7 @@ from .tm_utils import (NMS, GT_map, Get_pred_boxes, Make_Template_size_predictio
                        map_normalization)
 from .refine import SAM_box_refiner, mask_boxes  # noqa: F401
 from .maskhead import FusedMaskDecoder, mask_head, mask_head_weights  # noqa: F401
+from .twoway import FusedTwoWayTransformer, twoway_pool, twoway_update  # noqa: F401
 from .coco_gpu import APMeter, CocoEvalGPU  # noqa: F401
 
 __all__ = [
@@ -28,5 +29,6 @@ __all__ = [
     "calc_area", "map_normalization", "TMREngine", "PathConfig",
     "GT_map", "SetCriterion_TM", "build_criterion", "gIoU_loss", "WeightedFocalLoss",
     "SAM_box_refiner", "mask_boxes", "FusedMaskDecoder", "mask_head", "mask_head_weights", "CocoEvalGPU", "APMeter",
+    "FusedTwoWayTransformer", "twoway_pool", "twoway_update",
     "TMRError", "build_backbone", "register_backbone", "unregister_backbone", "FeatureInput",
 ]

@@ -208,6 +208,44 @@ MASK_HEAD_WPACK_BYTES = 9 * 32768 + 64  # TMR_MASK_HEAD_WPACK_BYTES
 MASK_HEAD_DIM = 256  # the one transformer_dim the kernel is built for
 
 
+class TwoWayPoolArgs(ctypes.Structure):
+    """tmr_twoway_pool_args_t (include/tmr_twoway.h)."""
+    _fields_ = [("keys", _P), ("pe", _P), ("qf", _P), ("ctx", _P), ("work", _P), ("N", _L), ("Nk", _L), ("P", _L),
+                ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("T", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class TwoWayUpdateArgs(ctypes.Structure):
+    """tmr_twoway_update_args_t (include/tmr_twoway.h)."""
+    _fields_ = [("keys_in", _P), ("pe", _P), ("A", _P), ("c", _P), ("B", _P), ("bo", _P), ("g", _P), ("beta", _P),
+                ("keys_out", _P), ("N", _L), ("Nk", _L), ("P", _L), ("C", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("T", ctypes.c_int32), ("eps", ctypes.c_float)]
+
+
+class TwoWayPlan(ctypes.Structure):
+    """tmr_twoway_plan_t (include/tmr_twoway.h)."""
+    _fields_ = [("variant", ctypes.c_int32), ("tile_pixels", ctypes.c_int32), ("chunk_pixels", ctypes.c_int32),
+                ("chunks", ctypes.c_int32), ("threads", ctypes.c_int32), ("lds_bytes", ctypes.c_int32),
+                ("blocks", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+# the two-way transformer's image side (include/tmr_twoway.h): same libtmr.so, outside the core ABI as well
+TWOWAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_twoway.h")
+TWOWAY_SIGNATURES = {
+    "tmr_twoway_pool": (_I, [ctypes.POINTER(TwoWayPoolArgs), _P]),
+    "tmr_twoway_update": (_I, [ctypes.POINTER(TwoWayUpdateArgs), _P]),
+    "tmr_twoway_pool_plan": (_I, [ctypes.POINTER(TwoWayPoolArgs), ctypes.POINTER(TwoWayPlan)]),
+    "tmr_twoway_update_plan": (_I, [ctypes.POINTER(TwoWayUpdateArgs), ctypes.POINTER(TwoWayPlan)]),
+}
+TWOWAY_VARIANTS = {0: "f32mfma"}  # TMR_TWOWAY_VARIANT_*
+TWOWAY_DIM, TWOWAY_HEADS, TWOWAY_ROWS = 256, 8, 64  # the one shape the kernels are built for; TMR_TWOWAY_ROWS
+TWOWAY_POOL_CHUNK = 512  # TMR_TWOWAY_POOL_CHUNK
+
+
+def twoway_pool_work_bytes(N: int, P: int) -> int:
+    """TMR_TWOWAY_POOL_WORK_BYTES(N, P)."""
+    return N * ((P + TWOWAY_POOL_CHUNK - 1) // TWOWAY_POOL_CHUNK) * TWOWAY_ROWS * (TWOWAY_DIM + 2) * 4
+
+
 class TMRError(RuntimeError):
     pass
 
@@ -226,7 +264,8 @@ def load() -> ctypes.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
-                                  + list(COCO_SIGNATURES.items()) + list(MASKHEAD_SIGNATURES.items())):
+                                  + list(COCO_SIGNATURES.items()) + list(MASKHEAD_SIGNATURES.items())
+                                  + list(TWOWAY_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -398,6 +437,62 @@ def mask_head_plan(**fields):
     N = 0 (the default) the geometry of (h, w) alone, whatever the pointers."""
     rc, plan = mask_head_plan_rc(**fields)
     check(rc, "tmr_mask_head_plan")
+    return plan
+
+
+def _twoway_defaults(fields):
+    fields.setdefault("C", TWOWAY_DIM)
+    fields.setdefault("H", TWOWAY_HEADS)
+    if "Nk" not in fields:
+        fields["Nk"] = fields.get("N", 0) or 1
+    return fields
+
+
+def twoway_pool(stream_=None, **fields) -> None:
+    """tmr_twoway_pool(&args, stream) (include/tmr_twoway.h)."""
+    a = _fill(TwoWayPoolArgs, "tmr_twoway_pool_args_t", _twoway_defaults(fields))
+    check(load().tmr_twoway_pool(ctypes.byref(a), stream_), "tmr_twoway_pool")
+
+
+def twoway_update(stream_=None, **fields) -> None:
+    """tmr_twoway_update(&args, stream) (include/tmr_twoway.h)."""
+    a = _fill(TwoWayUpdateArgs, "tmr_twoway_update_args_t", _twoway_defaults(fields))
+    check(load().tmr_twoway_update(ctypes.byref(a), stream_), "tmr_twoway_update")
+
+
+def _twoway_plan_rc(fn, struct, what, fields):
+    plan = TwoWayPlan()
+    rc = getattr(load(), fn)(ctypes.byref(_fill(struct, what, _twoway_defaults(fields))), ctypes.byref(plan))
+    if rc != 0:
+        return rc, None
+    out = {n: getattr(plan, n) for n, _ in TwoWayPlan._fields_ if n != "pad_"}
+    out["variant"] = TWOWAY_VARIANTS[plan.variant]
+    return rc, out
+
+
+def twoway_pool_plan_rc(**fields):
+    """tmr_twoway_pool_plan(&args, &plan) -> (return code, plan dict or None); host only.  Nk defaults
+    to N (1 when N = 0), C and H to 256 and 8."""
+    return _twoway_plan_rc("tmr_twoway_pool_plan", TwoWayPoolArgs, "tmr_twoway_pool_args_t", fields)
+
+
+def twoway_update_plan_rc(**fields):
+    """tmr_twoway_update_plan(&args, &plan) -> (return code, plan dict or None); host only."""
+    return _twoway_plan_rc("tmr_twoway_update_plan", TwoWayUpdateArgs, "tmr_twoway_update_args_t", fields)
+
+
+def twoway_pool_plan(**fields):
+    """twoway_pool_plan_rc's plan; raises TMRError where tmr_twoway_pool would refuse the call.  With
+    N = 0 (the default) the geometry of (P, T) alone, whatever the pointers."""
+    rc, plan = twoway_pool_plan_rc(**fields)
+    check(rc, "tmr_twoway_pool_plan")
+    return plan
+
+
+def twoway_update_plan(**fields):
+    """twoway_update_plan_rc's plan; raises TMRError where tmr_twoway_update would refuse the call."""
+    rc, plan = twoway_update_plan_rc(**fields)
+    check(rc, "tmr_twoway_update_plan")
     return plan
 
 

@@ -142,9 +142,16 @@ def mask_head(src, hyper, weights, size=None):
 class FusedMaskDecoder(nn.Module):
     """The reference's ``MaskDecoder`` (mask_decoder.py:16-161) with its mask
     head fused: same ``forward`` signature, same results (masks [N,1,4h,4w],
-    iou [N,1]).  Wraps the caller's decoder and owns no weights of its own."""
+    iou [N,1]).  Wraps the caller's decoder and owns no weights of its own.
 
-    def __init__(self, mask_decoder):
+    ``fuse_transformer=True`` also runs the decoder's two-way transformer
+    through ``FusedTwoWayTransformer`` (tmr_amd/twoway.py): its shared route
+    when one image embedding, one positional encoding and a batch-broadcast
+    dense prompt embedding serve every prompt (what ``SAM_box_refiner``
+    passes), its batched route otherwise.  ``transformer_calls`` then counts
+    the routes taken."""
+
+    def __init__(self, mask_decoder, fuse_transformer=False):
         super().__init__()
         dim = getattr(mask_decoder, "transformer_dim", None)
         if dim != MASK_HEAD_DIM:
@@ -165,6 +172,15 @@ class FusedMaskDecoder(nn.Module):
                 raise TMRError(f"FusedMaskDecoder: output_hypernetworks_mlps.{i} must end in {dim // 8} outputs")
         self.mask_decoder = mask_decoder
         self.weights = mask_head_weights(mask_decoder.output_upscaling)
+        self.fused_transformer = None
+        if fuse_transformer:
+            from .twoway import FusedTwoWayTransformer
+
+            self.fused_transformer = FusedTwoWayTransformer(mask_decoder.transformer)
+
+    @property
+    def transformer_calls(self):
+        return None if self.fused_transformer is None else self.fused_transformer.calls
 
     def forward(self, image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings,
                 multimask_output=False):
@@ -174,15 +190,35 @@ class FusedMaskDecoder(nn.Module):
         output_tokens = torch.cat([d.iou_token.weight, d.mask_tokens.weight], dim=0)
         output_tokens = output_tokens.unsqueeze(0).expand(sparse_prompt_embeddings.size(0), -1, -1)
         tokens = torch.cat((output_tokens, sparse_prompt_embeddings), dim=1)
+        ft = self.fused_transformer
+        if (ft is not None and image_embeddings.shape[0] == 1 and image_pe.shape[0] == 1
+                and (dense_prompt_embeddings.shape[0] == 1 or dense_prompt_embeddings.stride(0) == 0)):
+            # one embedding for every prompt: the add is done once, nothing is repeated
+            dense = dense_prompt_embeddings[:1]
+            if dense.shape[1:] != image_embeddings.shape[1:]:
+                dense = nn.UpsamplingBilinear2d(scale_factor=1.5)(dense)
+            src1 = image_embeddings + dense
+            if image_pe.shape[1:] != image_embeddings.shape[1:]:
+                image_pe = nn.UpsamplingBilinear2d(scale_factor=1.5)(image_pe)
+            h, w = src1.shape[2:]
+            hs, src = ft.forward_shared(src1, image_pe, tokens)
+            return self._head(hs, src, h, w)
         src = torch.repeat_interleave(image_embeddings, tokens.shape[0], dim=0)
         if dense_prompt_embeddings.shape[1:] != image_embeddings.shape[1:]:
             dense_prompt_embeddings = nn.UpsamplingBilinear2d(scale_factor=1.5)(dense_prompt_embeddings)
         src = src + dense_prompt_embeddings
         if image_pe.shape[1:] != image_embeddings.shape[1:]:
             image_pe = nn.UpsamplingBilinear2d(scale_factor=1.5)(image_pe)
-        pos_src = torch.repeat_interleave(image_pe, tokens.shape[0], dim=0)
+        if ft is not None and image_pe.shape[0] == 1:
+            pos_src = image_pe.expand(tokens.shape[0], -1, -1, -1)  # a broadcast: the wrapper sees it is shared
+        else:
+            pos_src = torch.repeat_interleave(image_pe, tokens.shape[0], dim=0)
         b, c, h, w = src.shape
-        hs, src = d.transformer(src, pos_src, tokens)
+        hs, src = (d.transformer if ft is None else ft)(src, pos_src, tokens)
+        return self._head(hs, src, h, w)
+
+    def _head(self, hs, src, h, w):
+        d = self.mask_decoder
         # token-sized: the IoU head, the selection, every MLP on all rows and the gather
         T = d.num_mask_tokens
         iou_pred = d.iou_prediction_head(hs[:, 0, :])
