@@ -430,6 +430,9 @@ int tmr_split_conv_points(const void *xp0, int C0, const int32_t *unit_image, co
                           const float *acc_init, const float *box, const int32_t *tiles, int ntiles, float *b,
                           int flags, void *stream);
 
+/* (tmr_points_chain.h, an extension outside this ABI: the per-image store launch and this launch at the
+ * points as one chain, without the slab between them) */
+
 /* ---- (a16) custom_shape_3x3_maxpool2d -----------------------------------
  * utils/TM_utils.py:337-361 on device fp32 planes x [planes][H][W]: out[e] =
  * the max over the 3x3 neighbourhood taps selected by mask9 (bit 3*r + c is

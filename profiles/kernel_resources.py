@@ -9,6 +9,11 @@ source digest of what was compiled (tests/test_points_resources_host.py holds
 the committed file to this tree's digest).  It reads the remarks only.
 
     python profiles/kernel_resources.py [OUT.json]
+    python profiles/kernel_resources.py --kernel split_points_chain_kernel [OUT.json]
+
+--kernel split_points_chain_kernel: the same figures of
+split_points_chain_kernel<3> (tmr_split_conv_points_chain, F16X3 only) into
+profiles/points_kloop/resources_chain.json.
 """
 import json
 import os
@@ -52,7 +57,11 @@ def remarks(hipcc, flags):
         return subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
 
 
-def parse(text):
+CHAIN = "split_points_chain_kernel"
+OUT_CHAIN = os.path.join(REPO, "profiles", "points_kloop", "resources_chain.json")
+
+
+def parse(text, kernel="split_points_kernel"):
     out, cur = {}, None
     for line in text.splitlines():
         m = re.search(r"remark: +([^:]+): (.*?) \[-Rpass-analysis", line)
@@ -60,22 +69,31 @@ def parse(text):
             continue
         key, val = m.group(1).strip(), m.group(2).strip()
         if key == "Function Name":
-            k = re.search(r"split_points_kernelILi3ELi(\d)EE", val)
-            cur = out.setdefault(PRECS[int(k.group(1))], {}) if k else None
+            if kernel == CHAIN:
+                cur = out.setdefault("F16X3", {}) if re.search(CHAIN + r"ILi3EE", val) else None
+            else:
+                k = re.search(r"split_points_kernelILi3ELi(\d)EE", val)
+                cur = out.setdefault(PRECS[int(k.group(1))], {}) if k else None
         elif cur is not None and key in FIELDS:
             cur[FIELDS[key]] = int(val)
     return out
 
 
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else OUT
+    argv = sys.argv[1:]
+    chain = argv[:2] == ["--kernel", CHAIN]
+    if chain:
+        argv = argv[2:]
+    out_path = argv[0] if argv else OUT_CHAIN if chain else OUT
     hipcc, flags = makefile_flags()
-    kernels = parse(remarks(hipcc, flags))
-    assert sorted(kernels) == sorted(PRECS.values()), kernels
+    kernels = parse(remarks(hipcc, flags), CHAIN if chain else "split_points_kernel")
+    assert sorted(kernels) == (["F16X3"] if chain else sorted(PRECS.values())), kernels
     load_package()
     from tmr_amd import buildinfo
-    rec = {"kernel": "split_points_kernel<3, PREC>", "flags": flags, "source_digest": buildinfo.source_digest("heads"),
-           "kernels": kernels, "parent": PARENT}
+    rec = {"kernel": "split_points_chain_kernel<3>" if chain else "split_points_kernel<3, PREC>", "flags": flags,
+           "source_digest": buildinfo.source_digest("heads"), "kernels": kernels}
+    if not chain:
+        rec["parent"] = PARENT
     os.makedirs(os.path.dirname(out_path), exist_ok=True)
     with open(out_path, "w") as f:
         json.dump(rec, f, indent=1)

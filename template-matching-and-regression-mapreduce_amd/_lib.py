@@ -246,6 +246,14 @@ def twoway_pool_work_bytes(N: int, P: int) -> int:
     return N * ((P + TWOWAY_POOL_CHUNK - 1) // TWOWAY_POOL_CHUNK) * TWOWAY_ROWS * (TWOWAY_DIM + 2) * 4
 
 
+# decoder_b's chain at the candidates (include/tmr_points_chain.h): same libtmr.so, outside the core ABI as well
+POINTS_CHAIN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_points_chain.h")
+POINTS_CHAIN_SIGNATURES = {
+    "tmr_split_conv_points_chain": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I,
+                                         _I, _P, _P, _P, _P, _I, _P, _I, _P]),
+}
+
+
 class TMRError(RuntimeError):
     pass
 
@@ -265,7 +273,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
                                   + list(COCO_SIGNATURES.items()) + list(MASKHEAD_SIGNATURES.items())
-                                  + list(TWOWAY_SIGNATURES.items())):
+                                  + list(TWOWAY_SIGNATURES.items()) + list(POINTS_CHAIN_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

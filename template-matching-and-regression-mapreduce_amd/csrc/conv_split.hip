@@ -51,6 +51,8 @@
 
 #include "tmr_common.h"
 
+#include "../../include/tmr_points_chain.h"
+
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -901,8 +903,22 @@ struct PArgs {
     float *b;               // [U][4][H][W], written at the points only
 };
 
-template <int KS, int PREC>
-__global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
+// The chained form (tmr_split_conv_points_chain, CHAIN below): the shared
+// route's two launches in one accumulator chain per candidate, without the
+// acc0 slab between them.  Phase 0 is the per-image store launch (s.x0 / NC0
+// chunks, these weights, the image's scale xmax0[unit_image[u]], starting
+// from s.acc_init = the broadcast bias plane), phase 1 the heads launch
+// (s.x1 / NC1 chunks, s.wp, s.wmax, the unit's s.xmax[u]).  Between them the
+// accumulator takes the two exact power-of-two multiplies the slab's store
+// and reload apply: acc * (1 / s_x0 s_w0), then * s_x1 s_w1, each rounded (or
+// under- / overflowing) on its own.
+struct CArgs {
+    const char *wp_fp;      // phase 0's packed weights [tap][NC0][Npad][WREC]
+    const float *wmax_fp, *xmax0;
+};
+
+template <int KS, int PREC, bool CHAIN>
+__device__ __forceinline__ void points_body(const PArgs &pa, const CArgs &ca) {
     typedef Prec<PREC> PR;
     typedef typename PR::V V;
     constexpr int T = KS * KS, HALVES = PR::HALVES, WREC = PR::WREC;
@@ -931,7 +947,8 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     // the block's two host tiles (column half hh = tile 2 * block + hh); a
     // half past the list repeats the block's first tile with no point to store
     int tu[2], tfirst[2], tcnt[2], timg[2];
-    float sxw[2];
+    float sxw[2];  // s_x s_w of the heads chain (CHAIN: of phase 1)
+    float sx0[2];  // CHAIN: s_x0 s_w0 of phase 0, the store launch's
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
         const int64_t ti = 2 * (int64_t)blockIdx.x + hh;
@@ -945,8 +962,13 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         timg[hh] = __builtin_amdgcn_readfirstlane(a.unit_image ? a.unit_image[tu[hh]] : tu[hh]);
         sxw[hh] = __builtin_bit_cast(
             float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, split_sxw<PREC>(a, tu[hh]))));
+        sx0[hh] = !CHAIN ? 1.0f : __builtin_bit_cast(
+            float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(
+                       int, split_scale(ca.xmax0 + timg[hh]) * split_scale(ca.wmax_fp))));
     }
-    const int NC = a.NC0 + a.NC1, NHC = NC * HALVES;
+    // the operands of the K loop that runs next: both sources in one chain,
+    // or (CHAIN) one source per phase (set_phase)
+    int NC = a.NC0 + a.NC1, NHC = NC * HALVES;
     // point p of a host tile: its pixel (a point past the tile's count repeats
     // a legal candidate row and is never stored; a pixel index is clamped into
     // the map, so no gather leaves the padded plane)
@@ -971,9 +993,21 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     };
     const char *xb0 = uniform_ptr(h0 ? a.x0 + (size_t)gimg * h0 * cstride : a.x1);  // h0 * cstride records
     const char *xb1 = uniform_ptr(h1 ? a.x1 + (size_t)gu * h1 * cstride : a.x0);    // h1 * cstride records
-    const uint32_t tapstride = (uint32_t)NC * a.Npad * WREC;
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
+    uint32_t tapstride = (uint32_t)NC * a.Npad * WREC;
+    __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
         (void *)a.wp, (short)0, T * tapstride, 0x00020000);
+    int p0 = h0, p1 = h1;  // half-chunk records of the two sources in the K loop that runs next
+    // CHAIN: the scalar operands of phase ph, swapped between the K loops
+    // (the one before is drained: its closing barrier, then the prologue's
+    // full wait)
+    auto set_phase = [&](int ph) {
+        NC = ph ? a.NC1 : a.NC0;
+        NHC = NC * HALVES;
+        p0 = ph ? 0 : h0;
+        p1 = ph ? h1 : 0;
+        tapstride = (uint32_t)NC * a.Npad * WREC;
+        wr = __builtin_amdgcn_make_buffer_rsrc((void *)(ph ? a.wp : ca.wp_fp), (short)0, T * tapstride, 0x00020000);
+    };
     // The gather of half-chunk hc into buffer hc & 1 by LDS-DMA: the KS wave
     // instructions of (ky, piece, half) fill the half's PT * KS slots of that
     // plane in image order, lane l of instruction i = slot 64 i + l = (point,
@@ -1015,10 +1049,10 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     // buffer that is not read again before the loop's closing barrier.
     auto gather = [&](int hc, bool live = true) {
         const int hcl = min(hc, NHC - 1);
-        const bool s0 = hcl < h0;
-        const uint32_t hs_ = (uint32_t)(s0 ? hcl : hcl - h0) * cstride + wt * qstride;
+        const bool s0 = hcl < p0;
+        const uint32_t hs_ = (uint32_t)(s0 ? hcl : hcl - p0) * cstride + wt * qstride;
         const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(s0 ? xb0 : xb1), (short)0, live ? (s0 ? h0 : h1) * cstride : 0, 0x00020000);
+            (void *)(s0 ? xb0 : xb1), (short)0, live ? (s0 ? p0 : p1) * cstride : 0, 0x00020000);
 #pragma unroll
         for (int ky = 0; ky < KS; ++ky)
 #pragma unroll
@@ -1044,81 +1078,7 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
         const int nt = a.NT0 + (active ? wtile : 0);
         const int lp = lane_now(), l16p = lp & 15, kgp = lp >> 4;
         uint32_t aoff = (uint32_t)kgp * a.Npad * 16 + ((uint32_t)nt * BM + wh * (BM / 2) + l16p) * 16;
-        // (pass 1: buffer 0 was last read before the K loop's closing barrier;
-        // the odd waves' sums of pass 0 sit in buffer 1)
-        gather(0);
-
         f32x4 acc[NF][PCG];
-        if (a.acc_init) {  // tiled (host-checked): the dense kernel's element of slab / tile / wave / lane
-            constexpr int HJ = PCG / 2;  // column groups per host tile
-            // (formed per pass: hoisted out of the pass loop, the pixels, the
-            // flags' tests and the reciprocal of W would cross the K loop)
-            int Wd = a.W, fl = a.flags;
-            asm volatile("" : "+s"(Wd), "+s"(fl));
-            // lane l reads the pixel of point l of each host tile once; a
-            // column's lane takes it from there
-            const int ppix[2] = {pixel(tu[0], tfirst[0], tcnt[0], lp), pixel(tu[1], tfirst[1], tcnt[1], lp)};
-            // 16-B group index of column group j's element (wave wpix * WNS + wh, in 0): + f * 8 groups of 64
-            auto group4 = [&](int j) {
-                const int hh = j / HJ;
-                const int pix = lane_read(ppix[hh], (j % HJ) * 16 + l16p);
-                const int py = pix / Wd, px = pix - py * Wd;
-                const int islab = (fl & TMR_SPLIT_INIT_BCAST) ? 0 : timg[hh];
-                const int mt = (py / TH) * a.TXN + px / TW;
-                const int wpix = (py % TH) >> 2, jp = ((py & 3) << 1) | ((px % TW) >> 4);
-                // = (((((size_t)islab * a.NT + nt) * a.MT + mt) * NWAVES + wpix * WNS + wh) * ACCW) / 4 + jp * 64
-                // + kgp * 16 + (px & 15), the lane's part put together from 32-bit halves (H W < 2^29: row <
-                // 2^23; in < ACCW / 4): a 64-bit lane sum takes a zero high half that would cross the K loop
-                static_assert(ACCW / 4 == 1 << 11 && 8 * 64 <= ACCW / 4, "the shifts below");
-                const uint32_t row = (uint32_t)(mt * NWAVES + wpix * WNS + wh), in = jp * 64 + kgp * 16 + (px & 15);
-                typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-                u2 lh = {row << 11 | in, row >> 21};
-                asm volatile("" : "+v"(lh));  // (opaque, or the sum is taken apart again)
-                return ((size_t)islab * a.NT + nt) * a.MT * NWAVES * (ACCW / 4) + __builtin_bit_cast(uint64_t, lh);
-            };
-            // one column group at a time, pinned: its address arithmetic is
-            // dead before the next group's starts (unpinned, the scheduler
-            // hoists the eight groups' together and spills them); the loads
-            // all fly before the first is scaled
-            if (fl & TMR_SPLIT_INIT_BF16) {  // (the raw pairs wait in the accumulator's first two registers)
-#pragma unroll
-                for (int j = 0; j < PCG; ++j) {
-                    const b4 *ai = reinterpret_cast<const b4 *>(a.acc_init) + group4(j);
-#pragma unroll
-                    for (int f = 0; f < NF; ++f) {
-                        const f2 raw = __builtin_bit_cast(f2, ai[f * 8 * 64]);
-                        acc[f][j] = (f32x4){raw.x, raw.y, 0.0f, 0.0f};
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int j = 0; j < PCG; ++j)
-#pragma unroll
-                    for (int f = 0; f < NF; ++f)
-                        acc[f][j] = __builtin_convertvector(__builtin_bit_cast(b4, (f2){acc[f][j][0], acc[f][j][1]}),
-                                                            f32x4) * sxw[j / HJ];
-            } else {
-#pragma unroll
-                for (int j = 0; j < PCG; ++j) {
-                    const f32x4 *ai = reinterpret_cast<const f32x4 *>(a.acc_init) + group4(j);
-#pragma unroll
-                    for (int f = 0; f < NF; ++f) acc[f][j] = ai[f * 8 * 64];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int j = 0; j < PCG; ++j)
-#pragma unroll
-                    for (int f = 0; f < NF; ++f) acc[f][j] = acc[f][j] * sxw[j / HJ];
-            }
-        } else {
-            float zf = 0.0f;  // (a zero of this pass, not a zero quad held from pass to pass)
-            asm volatile("" : "+v"(zf));
-#pragma unroll
-            for (int f = 0; f < NF; ++f)
-#pragma unroll
-                for (int j = 0; j < PCG; ++j) acc[f][j] = (f32x4){zf, zf, zf, zf};
-        }
-
         // stage s of a chunk: F16X3 s < 2T: hi half-chunk, tap s / 2, term s % 2
         // (wh, wl); s >= 2T: lo half-chunk, tap s - 2T, wh.  One-term: tap s.
         auto st_part = [](int s) { return HALVES == 2 && s >= 2 * T ? 1 : 0; };
@@ -1144,69 +1104,168 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) ar[s % AR][f] = buffer_load16<V>(wr, aoff + f * 256, as);
         };
-#pragma unroll
-        for (int s = 0; s < AR - 1; ++s) load_stage(0, s);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
         // B fragments: a rolling window of BW column groups.  One-term: every
         // stage takes a new tap, so the window costs no LDS read and frees 16
         // registers; F16X3 holds the whole stage, which its wl stage reuses
         constexpr int BW = HALVES == 2 ? PCG : PCG / 2;
         static_assert(PCG % BW == 0, "a group's slot is j % BW in every stage");
         V bc[BW];
-        for (int c = 0; c < NC; ++c) {
-            // one voffset register for a stage's NF fragments: opaque per
-            // chunk, so that aoff + f * 256 is formed beside its load and
-            // f * 256 folds into the instruction's offset (hoisted out of the
-            // loop, the four sums hold four registers)
-            asm volatile("" : "+v"(aoff));
-            // likewise the two strides of a stage's soffset: the NS stage
-            // offsets are two scalar multiplies each, not NS scalar registers
-            // held (and spilled to lanes) across the loop
-            asm volatile("" : "+s"(ts), "+s"(npl));
+        // CHAIN: phase 0 (the image's records) and phase 1 (the unit's) run the
+        // same K loop one after the other on the same accumulators, each after
+        // its own prologue; otherwise the one chain over both sources (ph = 1)
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int hc = c * HALVES + st_part(s);
-                // the loads of stage s + AR - 1 stay ahead of this stage's MFMAs
-                // and behind the last stage's (unpinned, the scheduler hoists
-                // whole chunks of loads and spills the accumulators); at a
-                // half-chunk's first stage they go ahead of the next gather, so
-                // that no stage's wait for its weights (vmcnt counts in issue
-                // order) covers a gather issued less than AR - 1 stages before
-                load_stage(c, s + AR - 1);
-                if (st_first(s)) {
-                    gather(hc + 1, hc + 1 < NHC);
+        for (int ph = CHAIN ? 0 : 1; ph < 2; ++ph) {
+            if constexpr (CHAIN) {
+                set_phase(ph);
+                ts = tapstride;
+            }
+            // (pass 1: buffer 0 was last read before the K loop's closing barrier;
+            // the odd waves' sums of pass 0 sit in buffer 1)
+            gather(0);
+
+            if (CHAIN && ph) {
+                // the slab's store and reload: acc * inv0 (the store epilogue's), then
+                // * s_x1 s_w1 (the heads prologue's), two roundings
+                float i0[2], s1[2] = {sxw[0], sxw[1]};
 #pragma unroll
-                    for (int j = 0; j < BW; ++j) bc[j] = bfrag(hc, st_tap(s), j);
-                }
-                // A column group's B fragment is dead after its NF MFMAs: the
-                // fragment BW groups on in the half-chunk's stream (this
-                // stage's group j + BW, or the next stage's group j + BW - PCG)
-                // is read into its place; with the whole stage held (BW = PCG)
-                // a stage on the same tap reads nothing (a half-chunk's first
-                // B waits for its barrier, above)
-                __builtin_amdgcn_sched_barrier(0);
+                for (int hh = 0; hh < 2; ++hh)
+                    i0[hh] = __builtin_bit_cast(
+                        float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, 1.0f / sx0[hh])));
 #pragma unroll
-                for (int j = 0; j < PCG; ++j) {
+                for (int j = 0; j < PCG; ++j)
 #pragma unroll
-                    for (int f = 0; f < NF; ++f) acc[f][j] = mma(ar[s % AR][f], bc[j % BW], acc[f][j]);
-                    if (j + BW < PCG) {
-                        bc[j % BW] = bfrag(hc, st_tap(s), j + BW);
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else if (!st_last(s) && (BW < PCG || st_newb(s + 1))) {
-                        bc[j % BW] = bfrag(hc, st_tap(s + 1), j + BW - PCG);
+                    for (int f = 0; f < NF; ++f) acc[f][j] = acc[f][j] * i0[j / (PCG / 2)];
+#pragma unroll
+                for (int j = 0; j < PCG; ++j)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) acc[f][j] = acc[f][j] * s1[j / (PCG / 2)];
+            } else if (a.acc_init) {  // tiled (host-checked): the dense kernel's element of slab / tile / wave / lane
+                constexpr int HJ = PCG / 2;  // column groups per host tile
+                // (formed per pass: hoisted out of the pass loop, the pixels, the
+                // flags' tests and the reciprocal of W would cross the K loop)
+                int Wd = a.W, fl = a.flags;
+                asm volatile("" : "+s"(Wd), "+s"(fl));
+                // lane l reads the pixel of point l of each host tile once; a
+                // column's lane takes it from there
+                const int ppix[2] = {pixel(tu[0], tfirst[0], tcnt[0], lp), pixel(tu[1], tfirst[1], tcnt[1], lp)};
+                // 16-B group index of column group j's element (wave wpix * WNS + wh, in 0): + f * 8 groups of 64
+                auto group4 = [&](int j) {
+                    const int hh = j / HJ;
+                    const int pix = lane_read(ppix[hh], (j % HJ) * 16 + l16p);
+                    const int py = pix / Wd, px = pix - py * Wd;
+                    const int islab = (fl & TMR_SPLIT_INIT_BCAST) ? 0 : timg[hh];
+                    const int mt = (py / TH) * a.TXN + px / TW;
+                    const int wpix = (py % TH) >> 2, jp = ((py & 3) << 1) | ((px % TW) >> 4);
+                    // = (((((size_t)islab * a.NT + nt) * a.MT + mt) * NWAVES + wpix * WNS + wh) * ACCW) / 4 + jp * 64
+                    // + kgp * 16 + (px & 15), the lane's part put together from 32-bit halves (H W < 2^29: row <
+                    // 2^23; in < ACCW / 4): a 64-bit lane sum takes a zero high half that would cross the K loop
+                    static_assert(ACCW / 4 == 1 << 11 && 8 * 64 <= ACCW / 4, "the shifts below");
+                    const uint32_t row = (uint32_t)(mt * NWAVES + wpix * WNS + wh), in = jp * 64 + kgp * 16 + (px & 15);
+                    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+                    u2 lh = {row << 11 | in, row >> 21};
+                    asm volatile("" : "+v"(lh));  // (opaque, or the sum is taken apart again)
+                    return ((size_t)islab * a.NT + nt) * a.MT * NWAVES * (ACCW / 4) + __builtin_bit_cast(uint64_t, lh);
+                };
+                // one column group at a time, pinned: its address arithmetic is
+                // dead before the next group's starts (unpinned, the scheduler
+                // hoists the eight groups' together and spills them); the loads
+                // all fly before the first is scaled
+                if (fl & TMR_SPLIT_INIT_BF16) {  // (the raw pairs wait in the accumulator's first two registers)
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j) {
+                        const b4 *ai = reinterpret_cast<const b4 *>(a.acc_init) + group4(j);
+#pragma unroll
+                        for (int f = 0; f < NF; ++f) {
+                            const f2 raw = __builtin_bit_cast(f2, ai[f * 8 * 64]);
+                            acc[f][j] = (f32x4){raw.x, raw.y, 0.0f, 0.0f};
+                        }
                         __builtin_amdgcn_sched_barrier(0);
                     }
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j)
+#pragma unroll
+                        for (int f = 0; f < NF; ++f)
+                            acc[f][j] = __builtin_convertvector(__builtin_bit_cast(b4, (f2){acc[f][j][0], acc[f][j][1]}),
+                                                                f32x4) * (CHAIN ? sx0[j / HJ] : sxw[j / HJ]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j) {
+                        const f32x4 *ai = reinterpret_cast<const f32x4 *>(a.acc_init) + group4(j);
+#pragma unroll
+                        for (int f = 0; f < NF; ++f) acc[f][j] = ai[f * 8 * 64];
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j)
+#pragma unroll
+                        for (int f = 0; f < NF; ++f) acc[f][j] = acc[f][j] * (CHAIN ? sx0[j / HJ] : sxw[j / HJ]);
                 }
-                __builtin_amdgcn_sched_barrier(0);
-                if (st_last(s)) {
-                    // the next half-chunk's gather has landed (it is older than
-                    // the (AR - 1) NF weight loads that may stay in flight: a
-                    // half-chunk has more than AR - 1 stages); this one's buffer
-                    // is free
-                    static_assert((AR - 1) * NF == 8 && T > AR - 1, "the counted wait below");
-                    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                    __syncthreads();
+            } else {
+                float zf = 0.0f;  // (a zero of this pass, not a zero quad held from pass to pass)
+                asm volatile("" : "+v"(zf));
+#pragma unroll
+                for (int f = 0; f < NF; ++f)
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j) acc[f][j] = (f32x4){zf, zf, zf, zf};
+            }
+#pragma unroll
+            for (int s = 0; s < AR - 1; ++s) load_stage(0, s);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            for (int c = 0; c < NC; ++c) {
+                // one voffset register for a stage's NF fragments: opaque per
+                // chunk, so that aoff + f * 256 is formed beside its load and
+                // f * 256 folds into the instruction's offset (hoisted out of the
+                // loop, the four sums hold four registers)
+                asm volatile("" : "+v"(aoff));
+                // likewise the two strides of a stage's soffset: the NS stage
+                // offsets are two scalar multiplies each, not NS scalar registers
+                // held (and spilled to lanes) across the loop
+                asm volatile("" : "+s"(ts), "+s"(npl));
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int hc = c * HALVES + st_part(s);
+                    // the loads of stage s + AR - 1 stay ahead of this stage's MFMAs
+                    // and behind the last stage's (unpinned, the scheduler hoists
+                    // whole chunks of loads and spills the accumulators); at a
+                    // half-chunk's first stage they go ahead of the next gather, so
+                    // that no stage's wait for its weights (vmcnt counts in issue
+                    // order) covers a gather issued less than AR - 1 stages before
+                    load_stage(c, s + AR - 1);
+                    if (st_first(s)) {
+                        gather(hc + 1, hc + 1 < NHC);
+#pragma unroll
+                        for (int j = 0; j < BW; ++j) bc[j] = bfrag(hc, st_tap(s), j);
+                    }
+                    // A column group's B fragment is dead after its NF MFMAs: the
+                    // fragment BW groups on in the half-chunk's stream (this
+                    // stage's group j + BW, or the next stage's group j + BW - PCG)
+                    // is read into its place; with the whole stage held (BW = PCG)
+                    // a stage on the same tap reads nothing (a half-chunk's first
+                    // B waits for its barrier, above)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < PCG; ++j) {
+#pragma unroll
+                        for (int f = 0; f < NF; ++f) acc[f][j] = mma(ar[s % AR][f], bc[j % BW], acc[f][j]);
+                        if (j + BW < PCG) {
+                            bc[j % BW] = bfrag(hc, st_tap(s), j + BW);
+                            __builtin_amdgcn_sched_barrier(0);
+                        } else if (!st_last(s) && (BW < PCG || st_newb(s + 1))) {
+                            bc[j % BW] = bfrag(hc, st_tap(s + 1), j + BW - PCG);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (st_last(s)) {
+                        // the next half-chunk's gather has landed (it is older than
+                        // the (AR - 1) NF weight loads that may stay in flight: a
+                        // half-chunk has more than AR - 1 stages); this one's buffer
+                        // is free
+                        static_assert((AR - 1) * NF == 8 && T > AR - 1, "the counted wait below");
+                        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                        __syncthreads();
+                    }
                 }
             }
         }
@@ -1311,13 +1370,36 @@ __global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
     }
 }
 
+template <int KS, int PREC>
+__global__ __launch_bounds__(NTHREADS) void split_points_kernel(PArgs pa) {
+    points_body<KS, PREC, false>(pa, CArgs{});
+}
+
+// the chained form: F16X3 only (a bf16 acc0 slab's rounding between the
+// phases is not reproduced here)
+template <int KS>
+__global__ __launch_bounds__(NTHREADS) void split_points_chain_kernel(PArgs pa, CArgs ca) {
+    points_body<KS, TMR_PREC_F16X3, true>(pa, ca);
+}
+
+constexpr size_t POINTS_LDS = 2 * 9 * P * PP * 16 + NWAVES * 4 * PP * sizeof(float);
+static_assert(POINTS_LDS <= LDS_KB * 1024, "LDS");
+
 template <int PREC>
 int launch_points(const PArgs &pa, int ntiles, hipStream_t s) {
-    constexpr size_t lds = 2 * 9 * P * PP * 16 + NWAVES * 4 * PP * sizeof(float);
-    static_assert(lds <= LDS_KB * 1024, "LDS");
+    constexpr size_t lds = POINTS_LDS;
     auto kern = split_points_kernel<3, PREC>;
     if (tmr_set_max_lds((const void *)kern, lds) != hipSuccess) return TMR_E_HIP;
     hipLaunchKernelGGL(kern, dim3((unsigned)((ntiles + 1) / 2)), dim3(NTHREADS), lds, s, pa);
+    TMR_CHECK_LAUNCH();
+    return TMR_OK;
+}
+
+int launch_points_chain(const PArgs &pa, const CArgs &ca, int ntiles, hipStream_t s) {
+    constexpr size_t lds = POINTS_LDS;
+    auto kern = split_points_chain_kernel<3>;
+    if (tmr_set_max_lds((const void *)kern, lds) != hipSuccess) return TMR_E_HIP;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((ntiles + 1) / 2)), dim3(NTHREADS), lds, s, pa, ca);
     TMR_CHECK_LAUNCH();
     return TMR_OK;
 }
@@ -1927,4 +2009,60 @@ extern "C" int tmr_split_conv_points(const void *xp0, int C0, const int32_t *uni
         case TMR_PREC_BF16: return launch_points<TMR_PREC_BF16>(pa, ntiles, s);
         default: return launch_points<TMR_PREC_F16>(pa, ntiles, s);
     }
+}
+
+// The shared route's store launch + heads launch + reduce at the points of
+// `tiles`, as one accumulator chain per candidate and without the acc0 slab
+// (tmr.h).  TMR_PREC_F16X3, ks = 3 and at most 8 channel tiles; anything else
+// is TMR_E_UNSUPPORTED and belongs to the store launch + tmr_split_conv_points.
+extern "C" int tmr_split_conv_points_chain(const void *xp0, int C0, const float *xmax0, const void *wpack_fp,
+                                           const float *wmax_fp, const float *bias_plane,
+                                           const int32_t *unit_image, const void *xp1, int C1, const float *xmax1,
+                                           const void *wpack, const float *wmax, int U, int H, int W, int ks,
+                                           int prec, const float *bias, int N, int leaky, const float *headw,
+                                           const float *head_bias, const float *box, const int32_t *tiles,
+                                           int ntiles, float *b, int flags, void *stream) {
+    TMR_REQUIRE(prec_ok(prec) && ks_ok(ks));
+    TMR_REQUIRE(xp0 && xmax0 && wpack_fp && wmax_fp && unit_image && xp1 && xmax1 && wpack && wmax);
+    TMR_REQUIRE(bias && headw && head_bias && box && b && U > 0 && H > 0 && W > 0 && N > 0 && C0 > 0 && C1 > 0);
+    TMR_REQUIRE(ntiles >= 0 && (ntiles == 0 || tiles));
+    TMR_REQUIRE((flags & 0xffff) == 0);  // the tile window only: the scales and the plane's form are fixed
+    TMR_REQUIRE((int64_t)H * W < (1ll << 29));
+    PArgs pa = {};
+    SArgs &a = pa.s;
+    a.x0 = static_cast<const char *>(xp0);
+    a.x1 = static_cast<const char *>(xp1);
+    a.unit_image = unit_image;
+    a.wp = static_cast<const char *>(wpack);
+    a.wmax = wmax;
+    a.xmax = xmax1;
+    a.bias = bias;
+    a.headw = headw;
+    a.acc_init = bias_plane;
+    a.NC0 = (int)tmr_cdiv(C0, CCH);
+    a.NC1 = (int)tmr_cdiv(C1, CCH);
+    a.U = U;
+    a.H = H;
+    a.W = W;
+    a.N = N;
+    a.NT = (int)tmr_cdiv(N, BM);
+    a.Npad = a.NT * BM;
+    a.TXN = (int)tmr_cdiv(W, TW);
+    a.MT = a.TXN * (int)tmr_cdiv(H, TH);
+    a.Hp = pad_h(H, ks);
+    a.Wp = pad_w(W, ks);
+    a.leaky = leaky;
+    // one scale per image (phase 0) and per unit (phase 1); the plane is one tiled fp32 slab
+    a.flags = TMR_SPLIT_XMAX_PER_UNIT | (bias_plane ? TMR_SPLIT_TILED_INIT | TMR_SPLIT_INIT_BCAST : 0);
+    a.EI = 1;
+    TMR_REQUIRE(tile_window(flags, a.NT, a.NT0, a.NTW));
+    if (prec != TMR_PREC_F16X3 || ks != 3 || a.NTW > 2 * PTW) return TMR_E_UNSUPPORTED;
+    pa.head_bias = head_bias;
+    pa.box = box;
+    pa.tiles = tiles;
+    pa.ntiles = ntiles;
+    pa.b = b;
+    CArgs ca = {static_cast<const char *>(wpack_fp), wmax_fp, xmax0};
+    if (ntiles == 0) return TMR_OK;
+    return launch_points_chain(pa, ca, ntiles, tmr_stream(stream));
 }

@@ -48,6 +48,9 @@ class DecoderPlan:
     init_flags: int  # the heads launch's initial-value and scale bits
     epi: int        # its image-major bits
     skip_tiles: int  # box_later: decoder_b's leading 128-channel tiles, left to the regression launches
+    # box_later, shared + folded, fp32: the fp-half launch leaves decoder_b's tiles out as well; after the finder
+    # they are computed at the candidates (tmr_split_conv_points_chain) or by a late store launch (fp_window)
+    fp_late: bool = False
 
     def window(self, ntiles: int) -> Tuple[int, int]:
         """(first, count) of the heads launch's channel tiles; (0, 0) = all."""
@@ -59,11 +62,24 @@ class DecoderPlan:
     def points_flags(self) -> int:
         return self.init_flags | split_tile_window(0, self.skip_tiles)
 
+    def fp_window(self, ntiles: int, late: bool = False) -> Tuple[int, int]:
+        """(first, count) of the fp-half launch's channel tiles: every tile, or (fp_late) decoder_o's before the
+        finder and decoder_b's in the late launch."""
+        if not self.fp_late:
+            return (0, 0)
+        return (0, self.skip_tiles) if late else (self.skip_tiles, ntiles - self.skip_tiles)
+
+    def fp_store_flags(self, ntiles: int, late: bool = False) -> int:
+        return self.fp_flags | split_tile_window(*self.fp_window(ntiles, late))
+
 
 def decoder_plan(cfg, fold_proj: bool, share_fp_half: bool, reuse_image_work: bool, have_feats: bool, U: int,
-                 B: int, unit_image, box_later: bool = False, nbt: int = 0) -> DecoderPlan:
+                 B: int, unit_image, box_later: bool = False, nbt: int = 0, fp_late: bool = False) -> DecoderPlan:
     """The route of decode() over U units of B images.  box_later: only the
-    tiles after decoder_b's nbt run in the heads launch."""
+    tiles after decoder_b's nbt run in the heads launch.  fp_late (asked for
+    by the engine above its floor): the fp-half launch leaves them out too,
+    where the chained points launch can stand in for it (shared, folded,
+    3-term fp16)."""
     fold = bool(cfg.fusion and fold_proj and have_feats)
     # share the fp half across an image's exemplars when that removes work
     # (U >= 2B), or when the module API keeps it for the image's next calls
@@ -85,7 +101,13 @@ def decoder_plan(cfg, fold_proj: bool, share_fp_half: bool, reuse_image_work: bo
         fp_flags, init = 0, plane
     return DecoderPlan(fold, share, acc16, bf16, SCALES_OWN if share else SCALES_MERGED if cfg.fusion else SCALES_FTM,
                        fp_flags, init | xpu, units_per_image(unit_image, B) << SPLIT_UNITS_PER_IMAGE_SHIFT,
-                       nbt if box_later else 0)
+                       nbt if box_later else 0,
+                       bool(fp_late and box_later and nbt > 0 and share and fold and cfg.precision == "fp32"))
+
+
+def fp_late_bound_macs(B: int, H: int, W: int, nbt: int, C0: int, ks: int) -> int:
+    """The most fp_late can save: the MACs of decoder_b's tiles of the fp-half launch."""
+    return B * H * W * 128 * nbt * C0 * ks * ks
 
 
 @dataclass
@@ -112,6 +134,7 @@ class HeadsLaunch:
     part: torch.Tensor
     plan: DecoderPlan
     b: Optional[torch.Tensor] = None  # box_later: the regression map still to fill
+    fp: Optional["FpHalf"] = None     # plan.fp_late: the fp-half launch's operands
 
     def _conv_args(self):
         return (ptr(self.xp0) if self.C0 else None, self.C0, ptr(self.ui), ptr(self.xp1), self.C1, self.U, self.H,
@@ -127,3 +150,34 @@ class HeadsLaunch:
         """decoder_b + ltrbs_head at the candidates of `tiles` only."""
         call("tmr_split_conv_points", *self._conv_args(), ptr(self.hb), ptr(self.a0), ptr(box), ptr(tiles), ntiles,
              ptr(self.b), self.plan.points_flags(), stream())
+
+    def run_points_chain(self, box: torch.Tensor, tiles: torch.Tensor, ntiles: int) -> None:
+        """The fp half's decoder_b tiles, decoder_b's f_TM half and ltrbs_head at the candidates, in one chain."""
+        f = self.fp
+        call("tmr_split_conv_points_chain", ptr(f.xp0), f.C0, ptr(f.xmax0), ptr(f.wp[0]), ptr(f.wp[1]),
+             ptr(f.bplane), ptr(self.ui), ptr(self.xp1), self.C1, ptr(self.xmax1), ptr(self.wp[0]), ptr(self.wp[1]),
+             self.U, self.H, self.W, self.ks, self.pc, ptr(self.bias), self.N, 1, ptr(self.hw), ptr(self.hb), ptr(box),
+             ptr(tiles), ntiles, ptr(self.b), split_tile_window(0, self.plan.skip_tiles), stream())
+
+
+@dataclass
+class FpHalf:
+    """The shared fp-half (store) launch: per image, into the acc0 slab the heads launch starts from."""
+    xp0: torch.Tensor
+    C0: int
+    B: int
+    H: int
+    W: int
+    ks: int
+    pc: int
+    wp: tuple  # (packed folded weights, max |w|)
+    xmax0: Optional[torch.Tensor]
+    zero_b: torch.Tensor
+    N: int
+    bplane: Optional[torch.Tensor]
+    acc0: torch.Tensor
+
+    def run(self, flags: int) -> None:
+        call("tmr_split_conv", ptr(self.xp0), self.C0, None, None, 0, self.B, self.H, self.W, self.ks, self.pc,
+             ptr(self.wp[0]), ptr(self.wp[1]), ptr(self.xmax0), ptr(self.zero_b), self.N, 0, None, ptr(self.bplane),
+             ptr(self.acc0), flags, stream())

@@ -32,7 +32,7 @@ from . import exp_table, graphs, host
 from ._lib import (PEAKS_DECODE_ONLY, PEAKS_FIND_ONLY, PEAKS_PROB_SCRATCH, POINTS_TILE, PREC_CODES, SPLIT_OUT_BF16,
                    SPLIT_TILED_OUT, SPLIT_XMAX_PER_PIXEL, UNIT_DTYPE, XCORR_ALGOS, TMRError, call, ptr, require_gpu,
                    size, stream, xcorr)
-from .decoder_plan import SCALES_FTM, SCALES_MERGED, HeadsLaunch, decoder_plan
+from .decoder_plan import SCALES_FTM, SCALES_MERGED, FpHalf, HeadsLaunch, decoder_plan, fp_late_bound_macs
 from .graphs import _clone_outputs, _GraphBook, _h2d, _units_to_device
 from .operands import absmax  # noqa: F401 -- unused here; tests written before operands.py import it from engine
 from .operands import (absmax_rows, conv2d_split, fold_proj, pack_split_up, pack_split_w, pack_split_x, pixel_absmax,
@@ -172,6 +172,7 @@ class TMREngine:
         self.last_points = 0
         self.last_points_flops = 0.0
         self._box_ctx: Optional[HeadsLaunch] = None  # decode(box_later=True)'s heads launch
+        self._fp_late_lost: Dict[tuple, bool] = {}  # box_fp_at_points "auto": shapes whose last call lost the cost rule
         if cfg.decoder_kernel_size not in (1, 3, 5, 7):
             raise TMRError("decoder_kernel_size must be 1, 3, 5 or 7")
 
@@ -427,8 +428,10 @@ class TMREngine:
         B, dev = fp.shape[0], f_tm.device
         ks, prec, pc = cfg.decoder_kernel_size, cfg.precision, prec_code(cfg.precision)
         # ---- plan: which launches, with which flags
+        nbt = self._box_tiles() if box_later else 0
         p = decoder_plan(cfg, self.fold_proj, self.share_fp_half, self.reuse_image_work, feats is not None, U, B,
-                         unit_image, box_later, self._box_tiles() if box_later else 0)
+                         unit_image, box_later, nbt, box_later and feats is not None and
+                         self._fp_at_points_wanted(B, H, W, nbt, feats.shape[1], ks, U))
         Cfp = fp.shape[1] if cfg.fusion else 0
         wp, bias, N, Cw, hw, hb, split, wbias = self._fused_decoders(Cfp if p.share else 0, p.fold)
         if Cw != Cfp + C1:
@@ -451,26 +454,30 @@ class TMREngine:
                     pack_split_x(fp, ks, prec, xmax0)
         xp1 = pack_split_x(f_tm, ks, prec, xmax1)
         # ---- launches: the fp half once per image, then the heads launch
+        fph, ntiles = None, (N + 127) // 128
         if p.share:
             wp_fp, wp, zero_b = split
             if acc0 is None:  # acc0 in the kernel's tiled accumulator layout (private)
                 acc0 = torch.empty(size("acc", B, N, H, W), device=dev, dtype=torch.float32)
-                call("tmr_split_conv", ptr(xp0), C0, None, None, 0, B, H, W, ks, pc, ptr(wp_fp[0]), ptr(wp_fp[1]),
-                     ptr(xmax0), ptr(zero_b), N, 0, None, ptr(bplane), ptr(acc0), p.fp_flags, stream())
+                fph = FpHalf(xp0, C0, B, H, W, ks, pc, wp_fp, xmax0, zero_b, N, bplane, acc0)
+                # (fp_late: decoder_o's tiles only; decoder_b's part of acc0 stays unwritten until a late store)
+                fph.run(p.fp_store_flags(ntiles))
                 if p.fold and self.reuse_image_work:
                     self._acc0_store(feats, split, H, W, acc0)
         part = torch.empty(size("heads_partials", N, U, H, W), device=dev, dtype=torch.float32)
         heads = HeadsLaunch(xp0=None if p.share else xp0, C0=0 if p.share else C0, ui=ui, xp1=xp1, C1=C1, U=U, H=H, W=W,
                             ks=ks, pc=pc, wp=wp, xmax1=xmax1, bias=bias, N=N, hw=hw, hb=hb,
-                            a0=acc0 if p.share else bplane, part=part, plan=p)
-        first, count = p.window((N + 127) // 128)
+                            a0=acc0 if p.share else bplane, part=part, plan=p, fp=fph if p.fp_late else None)
+        first, count = p.window(ntiles)
         with _timed(self.decoder_events):
             heads.run(first, count)
         # direct conv FLOPs of the timed launch's channel tiles (the kernel
         # executes 3 16-bit MFMA terms per product under the fp32 contract)
         n_run = 128 * count if box_later else N
         self.last_decoder_flops = 2.0 * H * W * n_run * (heads.C0 + C1) * ks ** 2 * U
-        self.last_shared_flops = 2.0 * H * W * N * C0 * ks ** 2 * B if p.share else 0.0
+        # (the channels the fp-half launch ran: fp_late leaves decoder_b's to _detect_box_at_peaks)
+        n_fp = N - 128 * nbt if p.fp_late else N
+        self.last_shared_flops = 2.0 * H * W * n_fp * C0 * ks ** 2 * B if p.share else 0.0
         self.last_decoder_algo = "split"
         # o and b as contiguous views of ONE buffer (a graph replay then
         # copies both out with one copy, _clone_outputs)
@@ -518,6 +525,49 @@ class TMREngine:
     # 0.57-0.66, one term 0.48 (bf16; f16 has no bench config and keeps bf16's)
     BOX_POINTS_CROSSOVER = {"fp32": 0.57, "bf16": 0.47, "f16": 0.47}
 
+    # ---- decoder_b's fp half only where the candidates are ---------------------
+    # On the route above with a shared, folded fp half (fp32 contract) the
+    # fp-half launch still computed decoder_b's tiles at every pixel of every
+    # image for the points launch to read a few percent of.  Above a floor it
+    # now runs decoder_o's tiles alone, and after the counts read-back the
+    # regression takes one of three routes: the chained points launch
+    # (tmr_split_conv_points_chain: both halves at the candidates, no acc0
+    # slab; "points_chain"), or decoder_b's store tiles now -- what the early
+    # launch would have cost -- followed by the points launch ("points") or
+    # the dense tiles ("dense").  Values are bit-identical on every route.
+    box_fp_at_points = "auto"  # "auto" | "always" (no floor, no cost rule: tests) | "never"
+    # the cost rule's constants, measured on one box at configs B, D with two exemplars and E (profiles/points_chain/
+    # crossover.json, profiles/points_crossover.py --chain): ns the chain adds to the points launch per candidate
+    # (11.1-12.7), ns of decoder_b's store tiles per image pixel (9.2-9.3).  Config E (16 units per image: 0.86
+    # candidates per image pixel) takes the late store, B (0.17) and D2 (0.11) the chain
+    FP_CHAIN_NS_PER_POINT = 12.0
+    FP_STORE_NS_PER_PIXEL = 9.3
+    # the floor: decoder_b's store tiles in MACs (decoder_plan.fp_late_bound_macs) below which the launches keep
+    # today's order.  The same sweep over config B's shapes at 1..64 images: from 16 images on (6.18e11 MACs) the
+    # chain route beat the parent's by more than 3x the spread, at 8 images (0.9 of 12.2 ms) by less
+    FP_AT_POINTS_FLOOR_MACS = 6.1e11
+
+    def _fp_at_points_wanted(self, B: int, H: int, W: int, nbt: int, C0: int, ks: int, U: int = 0) -> bool:
+        """Whether the fp-half launch leaves decoder_b's tiles out.  "auto": above the floor, and not where the
+        last call of this shape (images, units, map) ended on a late store: two store launches cost a little more
+        than one (config E: +0.1..0.3 ms of 115), so a shape whose candidates keep losing the cost rule goes back
+        to today's order until a call's count says the chain would have won (_fp_late_note)."""
+        mode = self.box_fp_at_points
+        if mode not in ("auto", "always", "never"):
+            raise TMRError("box_fp_at_points must be 'auto', 'always' or 'never'")
+        return mode == "always" or \
+            (mode == "auto" and fp_late_bound_macs(B, H, W, nbt, C0, ks) >= self.FP_AT_POINTS_FLOOR_MACS and
+             not self._fp_late_lost.get((B, U, H, W), False))
+
+    def _fp_chain_wins(self, points: int, B: int, H: int, W: int) -> bool:
+        """The cost rule: the chain's added time at the candidates against the store tiles' over the images."""
+        return points * self.FP_CHAIN_NS_PER_POINT < B * H * W * self.FP_STORE_NS_PER_PIXEL
+
+    def _fp_late_note(self, B: int, U: int, H: int, W: int, wins: bool) -> None:
+        if len(self._fp_late_lost) >= 64:  # (shapes seen, bounded)
+            self._fp_late_lost.clear()
+        self._fp_late_lost[(B, U, H, W)] = not wins
+
     def _box_tiles(self) -> int:
         """decoder_b's 128-channel tiles at the front of decoder_b || decoder_o."""
         return int(self.P["decoder_b.layer.0.weight"].shape[0]) // 128
@@ -542,6 +592,18 @@ class TMREngine:
             td = _h2d(np.ascontiguousarray(tiles, np.int32).reshape(-1), box.device)
             self._box_ctx.run_points(box, td, len(tiles))
 
+    def box_chain_at_points(self, box: torch.Tensor, tiles: np.ndarray) -> None:
+        """b at the candidates of `tiles` with decoder_b's fp half computed there too (plan.fp_late: acc0 holds
+        decoder_o's tiles only)."""
+        if len(tiles):
+            td = _h2d(np.ascontiguousarray(tiles, np.int32).reshape(-1), box.device)
+            self._box_ctx.run_points_chain(box, td, len(tiles))
+
+    def box_late_store(self) -> None:
+        """decoder_b's tiles of the fp-half launch, left out before the finder (plan.fp_late)."""
+        h = self._box_ctx
+        h.fp.run(h.plan.fp_store_flags((h.N + 127) // 128, late=True))
+
     def box_dense(self) -> None:
         """b everywhere: decoder_b's tiles of the dense heads launch."""
         h = self._box_ctx
@@ -565,15 +627,26 @@ class TMREngine:
         self.last_points = int(need.sum())
         dense = self.box_at_peaks == "auto" and \
             self.last_points > self.BOX_POINTS_CROSSOVER[self.cfg.precision] * U * H * W
-        self.last_box_route = "dense" if dense else "points"
+        h = self._box_ctx
+        nbt = h.plan.skip_tiles
+        # fp_late: the chain where its added time at the candidates is under the store tiles' over the images
+        nimg = feats.shape[0]
+        wins = not dense and self._fp_chain_wins(self.last_points, nimg, H, W)
+        if self.box_fp_at_points == "auto":
+            self._fp_late_note(nimg, U, H, W, wins)
+        chain = h.plan.fp_late and not dense and (self.box_fp_at_points == "always" or wins)
+        self.last_box_route = "dense" if dense else "points_chain" if chain else "points"
+        if h.plan.fp_late and not chain:  # decoder_b's store tiles after all, at the early launch's cost
+            self.box_late_store()
+            self.last_shared_flops += 2.0 * H * W * 128 * nbt * h.fp.C0 * h.ks ** 2 * h.fp.B
         if dense:
             self.box_dense()
             self.last_points_flops = 0.0
         else:
             tiles = host.point_tiles(need, POINTS_TILE)
-            self.box_at_points(box, tiles)
-            h = self._box_ctx
-            self.last_points_flops = 2.0 * 128 * h.plan.skip_tiles * (h.C0 + h.C1) * h.ks ** 2 * POINTS_TILE * len(tiles)
+            (self.box_chain_at_points if chain else self.box_at_points)(box, tiles)
+            cin = (h.fp.C0 if chain else h.C0) + h.C1
+            self.last_points_flops = 2.0 * 128 * nbt * cin * h.ks ** 2 * POINTS_TILE * len(tiles)
         self._box_ctx = None
         self.peaks(o, b, params, want_prob=False, phase="decode", found=(logits, box, ref, counts))
         return logits, box, ref, counts, counts_host
