@@ -10,10 +10,15 @@ torchvision is absent from this image, so ``torchvision.ops.roi_align`` and
 ``torchvision.ops.nms`` are provided by stubs:
   * roi_align -> the C restatement (oracle/tmr_oracle.c); the stub also
     records the roi / output size the reference computed, which pins the
-    template sizing arithmetic (template_matching.py:56-75);
+    template sizing arithmetic (template_matching.py:56-75).  The `template`
+    fixture's values are therefore the oracle's own: what pins them is the
+    float64 definition in tests/roi_align_ref.py
+    (tests/test_third_party_pins_host.py), to 1e-5, not torchvision's bits;
   * nms -> an independent pure-Python transcription of torchvision 0.19's
-    CPU nms (below), so the NMS fixtures cross-check the C restatement but
-    stay UNPINNED against real torchvision.
+    CPU nms (below), so the NMS fixtures cross-check the C restatement.  The
+    greedy rule and the IoU are pinned to the float64 definition
+    (tests/nms_ref.py) on tie-free finite sets; the order of tied and
+    non-finite scores stays unpinned against real torchvision.
 
 Usage (in this container only; /root/reference does not exist on the GPU box):
     PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py
@@ -494,7 +499,9 @@ def main():
     R = import_reference()
     meta = dict(torch=torch.__version__, threads=torch.get_num_threads(), numpy=np.__version__,
                 reference="/root/reference @ 2026-01-16", generator="oracle/make_golden.py",
-                stubs="roi_align=oracle C restatement (unpinned); nms=py_nms transcription (unpinned)")
+                stubs="roi_align=oracle C restatement (pinned to the float64 definition, "
+                      "tests/roi_align_ref.py, not to torchvision's bits); nms=py_nms transcription "
+                      "(greedy rule pinned by tests/nms_ref.py; tie / non-finite order unpinned)")
     jobs = {"xcorr": lambda: gen_xcorr(R), "template": lambda: gen_template(R),
             "pred_boxes": lambda: gen_pred_boxes(R), "nms": lambda: gen_nms(R),
             "caller": lambda: gen_caller(R),

@@ -15,8 +15,14 @@
  * sizing, cross-correlation, peak finder, box decode) are pinned against
  * golden vectors produced by importing /root/reference (oracle/make_golden.py,
  * tests/golden/).  roi_align / nms restate torchvision==0.19.0 (a third-party
- * dependency absent from this image): parity there is UNPINNED (see
- * DESIGN.md "Oracle").
+ * dependency absent from this image), so no fixture of theirs comes from
+ * torchvision.  They are pinned to the operations' DEFINITIONS instead, by code
+ * that does not follow this file: tests/roi_align_ref.py (float64 on ATen's
+ * grid_sample, and a closed form on linear ramps) and tests/nms_ref.py (float64
+ * greedy), run by tests/test_third_party_pins_host.py.  Still unpinned:
+ * torchvision's order of tied / non-finite scores beyond py_nms's reading of it,
+ * and its rounding inside a bin (values are pinned to 1e-5, not bits).  See
+ * DESIGN.md "Oracle".
  */
 #include <math.h>
 #include <stdint.h>
@@ -68,8 +74,11 @@ void orc_prototype_box(const float box[4], int H, int W, int out[4]) {
 }
 
 /* ------------------------------------------------------------------------
- * RoIAlign, torchvision 0.19.0 CPU kernel semantics (third-party, UNPINNED),
- * called at models/template_matching.py:75 as
+ * RoIAlign, torchvision 0.19.0 CPU kernel semantics (third-party and absent:
+ * the half-pixel offset, the adaptive grid count, the divisor and the border
+ * clamp / outside-the-map rejection below are pinned to the definition by
+ * tests/test_third_party_pins_host.py, to 1e-5 normwise, not to torchvision's
+ * bits), called at models/template_matching.py:75 as
  *   roi_align(f[1,C,H,W], [[x1,y1,x2,y2]], (Ht,Wt), aligned=True)
  * spatial_scale = 1, sampling_ratio = -1 (adaptive), aligned offset 0.5.
  * SURVEY.md Appendix A.
@@ -313,8 +322,11 @@ int64_t orc_peaks_decode(const float *p, const float *reg, int H, int W,
 }
 
 /* ------------------------------------------------------------------------
- * Greedy NMS, torchvision 0.19.0 CPU nms kernel semantics (third-party,
- * UNPINNED), called at utils/TM_utils.py:322.  SURVEY.md Appendix B:
+ * Greedy NMS, torchvision 0.19.0 CPU nms kernel semantics (third-party and
+ * absent: the greedy rule and the IoU are pinned to the float64 definition on
+ * tie-free finite sets by tests/test_third_party_pins_host.py; tie and
+ * non-finite order only by py_nms's fixtures), called at utils/TM_utils.py:322.
+ * SURVEY.md Appendix B:
  * stable descending sort on score, IoU in fp32, compared in double.
  * ------------------------------------------------------------------------ */
 static const float *g_sort_scores;
