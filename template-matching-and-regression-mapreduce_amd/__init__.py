@@ -20,6 +20,7 @@ from .tm_utils import (NMS, GT_map, Get_pred_boxes, Make_Template_size_predictio
 from .refine import SAM_box_refiner, mask_boxes  # noqa: F401
 from .maskhead import FusedMaskDecoder, mask_head, mask_head_weights  # noqa: F401
 from .twoway import FusedTwoWayTransformer, twoway_pool, twoway_update  # noqa: F401
+from .tokens import tokens_back, tokens_front, tokens_tail  # noqa: F401
 from .coco_gpu import APMeter, CocoEvalGPU  # noqa: F401
 
 __all__ = [
@@ -30,5 +31,6 @@ __all__ = [
     "GT_map", "SetCriterion_TM", "build_criterion", "gIoU_loss", "WeightedFocalLoss",
     "SAM_box_refiner", "mask_boxes", "FusedMaskDecoder", "mask_head", "mask_head_weights", "CocoEvalGPU", "APMeter",
     "FusedTwoWayTransformer", "twoway_pool", "twoway_update",
+    "tokens_front", "tokens_back", "tokens_tail",
     "TMRError", "build_backbone", "register_backbone", "unregister_backbone", "FeatureInput",
 ]

@@ -246,6 +246,69 @@ def twoway_pool_work_bytes(N: int, P: int) -> int:
     return N * ((P + TWOWAY_POOL_CHUNK - 1) // TWOWAY_POOL_CHUNK) * TWOWAY_ROWS * (TWOWAY_DIM + 2) * 4
 
 
+class TokLinear(ctypes.Structure):
+    """tmr_tok_linear_t (include/tmr_tokens.h)."""
+    _fields_ = [("w", _P), ("b", _P), ("in_", ctypes.c_int32), ("out", ctypes.c_int32)]
+
+
+class TokAttn(ctypes.Structure):
+    """tmr_tok_attn_t (include/tmr_tokens.h)."""
+    _fields_ = [("q", TokLinear), ("k", TokLinear), ("v", TokLinear), ("o", TokLinear)]
+
+
+class TokNorm(ctypes.Structure):
+    """tmr_tok_norm_t (include/tmr_tokens.h)."""
+    _fields_ = [("g", _P), ("b", _P), ("eps", ctypes.c_float), ("pad_", ctypes.c_int32)]
+
+
+class TokMlp3(ctypes.Structure):
+    """tmr_tok_mlp3_t (include/tmr_tokens.h)."""
+    _fields_ = [("l", TokLinear * 3)]
+
+
+TOKENS_MAX_MASKS, TOKENS_HYPER_OUT, TOKENS_MLP_CHUNK = 8, 32, 512  # TMR_TOKENS_MAX_MASKS, _HYPER_OUT, _MLP_CHUNK
+
+
+class TokensFrontArgs(ctypes.Structure):
+    """tmr_tokens_front_args_t (include/tmr_tokens.h)."""
+    _fields_ = [("x", _P), ("p", _P), ("x1", _P), ("qf", _P), ("self_attn", TokAttn), ("norm1", TokNorm),
+                ("cross", TokAttn), ("N", _L), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("has_self_attn", ctypes.c_int32), ("skip_pe", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class TokensBackArgs(ctypes.Structure):
+    """tmr_tokens_back_args_t (include/tmr_tokens.h)."""
+    _fields_ = [("x1", _P), ("p", _P), ("ctx", _P), ("x_out", _P), ("A", _P), ("c", _P), ("B", _P), ("t2i", TokAttn),
+                ("norm", TokNorm), ("lin1", TokLinear), ("lin2", TokLinear), ("norm3", TokNorm), ("i2t", TokAttn),
+                ("N", _L), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("has_mlp", ctypes.c_int32)]
+
+
+class TokensTailArgs(ctypes.Structure):
+    """tmr_tokens_tail_args_t (include/tmr_tokens.h)."""
+    _fields_ = [("hs", _P), ("iou_pred", _P), ("hyper_all", _P), ("iou", TokMlp3), ("hyper", TokMlp3 * TOKENS_MAX_MASKS),
+                ("N", _L), ("C", ctypes.c_int32), ("T", ctypes.c_int32), ("M", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class TokensPlan(ctypes.Structure):
+    """tmr_tokens_plan_t (include/tmr_tokens.h)."""
+    _fields_ = [("variant", ctypes.c_int32), ("threads", ctypes.c_int32), ("lds_bytes", ctypes.c_int32),
+                ("blocks", ctypes.c_int32), ("prompts_per_block", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+# the mask decoder's token side (include/tmr_tokens.h): same libtmr.so, outside the core ABI as well
+TOKENS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_tokens.h")
+TOKENS_SIGNATURES = {
+    "tmr_tokens_front": (_I, [ctypes.POINTER(TokensFrontArgs), _P]),
+    "tmr_tokens_back": (_I, [ctypes.POINTER(TokensBackArgs), _P]),
+    "tmr_tokens_tail": (_I, [ctypes.POINTER(TokensTailArgs), _P]),
+    "tmr_tokens_front_plan": (_I, [ctypes.POINTER(TokensFrontArgs), ctypes.POINTER(TokensPlan)]),
+    "tmr_tokens_back_plan": (_I, [ctypes.POINTER(TokensBackArgs), ctypes.POINTER(TokensPlan)]),
+    "tmr_tokens_tail_plan": (_I, [ctypes.POINTER(TokensTailArgs), ctypes.POINTER(TokensPlan)]),
+}
+TOKENS_VARIANTS = {0: "f32mfma"}  # TMR_TOKENS_VARIANT_*
+
+
 # decoder_b's chain at the candidates (include/tmr_points_chain.h): same libtmr.so, outside the core ABI as well
 POINTS_CHAIN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "tmr_points_chain.h")
 POINTS_CHAIN_SIGNATURES = {
@@ -273,7 +336,8 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
                                   + list(COCO_SIGNATURES.items()) + list(MASKHEAD_SIGNATURES.items())
-                                  + list(TWOWAY_SIGNATURES.items()) + list(POINTS_CHAIN_SIGNATURES.items())):
+                                  + list(TWOWAY_SIGNATURES.items()) + list(POINTS_CHAIN_SIGNATURES.items())
+                                  + list(TOKENS_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -501,6 +565,81 @@ def twoway_update_plan(**fields):
     """twoway_update_plan_rc's plan; raises TMRError where tmr_twoway_update would refuse the call."""
     rc, plan = twoway_update_plan_rc(**fields)
     check(rc, "tmr_twoway_update_plan")
+    return plan
+
+
+def tok_linear(w, b, in_, out) -> TokLinear:
+    """tmr_tok_linear_t from two addresses (or None) and the layer's sizes."""
+    return TokLinear(w, b, int(in_), int(out))
+
+
+def tok_attn(q, k, v, o) -> TokAttn:
+    return TokAttn(q, k, v, o)
+
+
+def tok_norm(g, b, eps) -> TokNorm:
+    return TokNorm(g, b, float(eps), 0)
+
+
+def tok_mlp3(l0, l1, l2) -> TokMlp3:
+    return TokMlp3((TokLinear * 3)(l0, l1, l2))
+
+
+def _tokens_args(struct, what, fields):
+    """A tokens args struct from keyword fields: plain ones through _fill (C and H default to 256
+    and 8), descriptor structs (and the list `hyper`) assigned as they are."""
+    nested = {k: fields.pop(k) for k in list(fields) if isinstance(fields[k], (ctypes.Structure, list, tuple))}
+    names = {n for n, _ in struct._fields_}
+    if "C" in names:
+        fields.setdefault("C", TWOWAY_DIM)
+    if "H" in names:
+        fields.setdefault("H", TWOWAY_HEADS)
+    a = _fill(struct, what, fields)
+    for k, v in nested.items():
+        if k not in names:
+            raise TMRError(f"{what} has no field(s) {[k]}")
+        if k == "hyper":
+            if len(v) > TOKENS_MAX_MASKS:
+                raise TMRError(f"{what}: at most {TOKENS_MAX_MASKS} hypernetwork MLPs")
+            for i, m in enumerate(v):
+                a.hyper[i] = m
+        else:
+            setattr(a, k, v)
+    return a
+
+
+_TOKENS = {"front": (TokensFrontArgs, "tmr_tokens_front"), "back": (TokensBackArgs, "tmr_tokens_back"),
+           "tail": (TokensTailArgs, "tmr_tokens_tail")}
+
+
+def tokens_args(which: str, **fields):
+    """The args struct of tmr_tokens_<which> ("front", "back", "tail") from keyword fields."""
+    struct, fn = _TOKENS[which]
+    return _tokens_args(struct, fn + "_args_t", fields)
+
+
+def tokens_launch(which: str, stream_=None, **fields) -> None:
+    """tmr_tokens_<which>(&args, stream) (include/tmr_tokens.h)."""
+    struct, fn = _TOKENS[which]
+    check(getattr(load(), fn)(ctypes.byref(_tokens_args(struct, fn + "_args_t", fields)), stream_), fn)
+
+
+def tokens_plan_rc(which: str, **fields):
+    """tmr_tokens_<which>_plan(&args, &plan) -> (return code, plan dict or None); host only."""
+    struct, fn = _TOKENS[which]
+    plan = TokensPlan()
+    rc = getattr(load(), fn + "_plan")(ctypes.byref(_tokens_args(struct, fn + "_args_t", fields)), ctypes.byref(plan))
+    if rc != 0:
+        return rc, None
+    out = {n: getattr(plan, n) for n, _ in TokensPlan._fields_ if n != "pad_"}
+    out["variant"] = TOKENS_VARIANTS[plan.variant]
+    return rc, out
+
+
+def tokens_plan(which: str, **fields):
+    """tokens_plan_rc's plan; raises TMRError where the launch would refuse the call."""
+    rc, plan = tokens_plan_rc(which, **fields)
+    check(rc, f"tmr_tokens_{which}_plan")
     return plan
 
 

@@ -149,10 +149,18 @@ class FusedMaskDecoder(nn.Module):
     when one image embedding, one positional encoding and a batch-broadcast
     dense prompt embedding serve every prompt (what ``SAM_box_refiner``
     passes), its batched route otherwise.  ``transformer_calls`` then counts
-    the routes taken."""
+    the routes taken.
 
-    def __init__(self, mask_decoder, fuse_transformer=False):
+    ``fuse_tokens=True`` (with ``fuse_transformer=True``) also runs the token
+    side in HIP (tmr_amd/tokens.py): the transformer's through
+    ``FusedTwoWayTransformer(..., fuse_tokens=True)``, the IoU head and the
+    hypernetwork MLPs through ``tokens_tail``; the argmax and the two gathers
+    stay torch ops."""
+
+    def __init__(self, mask_decoder, fuse_transformer=False, fuse_tokens=False):
         super().__init__()
+        if fuse_tokens and not fuse_transformer:
+            raise TMRError("FusedMaskDecoder: fuse_tokens=True requires fuse_transformer=True")
         dim = getattr(mask_decoder, "transformer_dim", None)
         if dim != MASK_HEAD_DIM:
             raise TMRError(f"FusedMaskDecoder: transformer_dim is {dim}; the fused head is built for "
@@ -173,10 +181,17 @@ class FusedMaskDecoder(nn.Module):
         self.mask_decoder = mask_decoder
         self.weights = mask_head_weights(mask_decoder.output_upscaling)
         self.fused_transformer = None
+        self.fuse_tokens = bool(fuse_tokens)
+        if fuse_tokens:
+            from .tokens import check_mlp3
+
+            check_mlp3(mask_decoder.iou_prediction_head, "iou_prediction_head")
+            for i, mlp in enumerate(mlps):
+                check_mlp3(mlp, f"output_hypernetworks_mlps.{i}")
         if fuse_transformer:
             from .twoway import FusedTwoWayTransformer
 
-            self.fused_transformer = FusedTwoWayTransformer(mask_decoder.transformer)
+            self.fused_transformer = FusedTwoWayTransformer(mask_decoder.transformer, fuse_tokens=fuse_tokens)
 
     @property
     def transformer_calls(self):
@@ -221,9 +236,15 @@ class FusedMaskDecoder(nn.Module):
         d = self.mask_decoder
         # token-sized: the IoU head, the selection, every MLP on all rows and the gather
         T = d.num_mask_tokens
-        iou_pred = d.iou_prediction_head(hs[:, 0, :])
-        ids = torch.argmax(iou_pred, dim=1)
-        hyper_all = torch.stack([d.output_hypernetworks_mlps[i](hs[:, 1 + i, :]) for i in range(T)], dim=1)
+        if self.fuse_tokens:
+            from .tokens import tokens_tail
+
+            iou_pred, hyper_all = tokens_tail(hs, d.iou_prediction_head, d.output_hypernetworks_mlps)
+            ids = torch.argmax(iou_pred, dim=1)
+        else:
+            iou_pred = d.iou_prediction_head(hs[:, 0, :])
+            ids = torch.argmax(iou_pred, dim=1)
+            hyper_all = torch.stack([d.output_hypernetworks_mlps[i](hs[:, 1 + i, :]) for i in range(T)], dim=1)
         hyper = torch.gather(hyper_all, 1, ids.view(-1, 1, 1).expand(-1, 1, hyper_all.shape[2]))[:, 0]
         iou = torch.gather(iou_pred, 1, ids.view(-1, 1))
         if src.dtype != torch.float32:

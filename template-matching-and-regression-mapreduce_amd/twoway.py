@@ -13,7 +13,10 @@ cross-attentions fold so that the image side needs no projection weights
 
 Self-attention, the MLP, the token-side norms, the folding and the value /
 output projections after pooling are torch ops on token-sized tensors; the
-kernels see no weights, so nothing is packed or version-tracked.
+kernels see no weights, so nothing is packed or version-tracked.  With
+``fuse_tokens=True`` that token side runs in HIP as well (tmr_amd/tokens.py:
+``tokens_front`` and ``tokens_back`` on the live parameters), about 15 launches
+per forward instead of about 120.
 
 ``FusedTwoWayTransformer`` is the drop-in for the caller's ``TwoWayTransformer``:
 
@@ -200,13 +203,25 @@ class FusedTwoWayTransformer(nn.Module):
     Wraps the caller's module and owns no weights.  ``forward_shared`` is the
     route for one image embedding shared by every prompt (what the refiner
     has): layer 0 reads the one [h*w,256] tensor instead of N copies.
-    ``calls`` counts the routes taken ("shared", "batched", "stock")."""
+    ``calls`` counts the routes taken ("shared", "batched", "stock").
 
-    def __init__(self, transformer):
+    ``fuse_tokens=True`` runs the token side of the fused routes through
+    ``tokens_front`` / ``tokens_back`` (tmr_amd/tokens.py) instead of torch ops;
+    ``token_calls`` counts the forwards that did."""
+
+    def __init__(self, transformer, fuse_tokens=False):
         super().__init__()
         check_transformer(transformer)
+        if fuse_tokens:
+            from .tokens import check_mlp_block
+
+            for i, blk in enumerate(transformer.layers):
+                _check_attention(blk.self_attn, f"layers.{i}.self_attn", TWOWAY_DIM)
+                check_mlp_block(blk.mlp, f"layers.{i}.mlp")
         self.transformer = transformer
+        self.fuse_tokens = bool(fuse_tokens)
         self.calls = {"shared": 0, "batched": 0, "stock": 0}
+        self.token_calls = 0
 
     def forward(self, image_embedding, image_pe, point_embedding):
         require_gpu(image_embedding, "image_embedding")
@@ -251,6 +266,8 @@ class FusedTwoWayTransformer(nn.Module):
         if keys.dtype != torch.float32 or point_embedding.dtype != torch.float32:
             raise TMRError("FusedTwoWayTransformer: fp32 only")
         N, T = int(point_embedding.shape[0]), int(point_embedding.shape[1])
+        if self.fuse_tokens:
+            return self._run_tokens(keys, pe, point_embedding, own)
         queries = point_embedding
         for blk in tr.layers:
             if blk.skip_first_layer_pe:
@@ -273,3 +290,28 @@ class FusedTwoWayTransformer(nn.Module):
         ctx = twoway_pool(keys, pe, fold_tokens_to_image(att, queries + point_embedding), T)
         queries = tr.norm_final_attn(queries + unfold_context(att, ctx, T))
         return queries, keys
+
+    def _run_tokens(self, keys, pe, point_embedding, own):
+        """_run with the token side in HIP: per layer front, pool, back, update."""
+        from .tokens import tokens_back, tokens_front
+
+        tr = self.transformer
+        N, T = int(point_embedding.shape[0]), int(point_embedding.shape[1])
+        self.token_calls += 1
+        pts = queries = point_embedding.detach().contiguous()
+        for blk in tr.layers:
+            att = blk.cross_attn_token_to_image
+            queries, qf = tokens_front(queries, pts, att, self_attn=blk.self_attn, norm1=blk.norm1,
+                                       skip_pe=blk.skip_first_layer_pe)
+            ctx = twoway_pool(keys, pe, qf, T)
+            att2 = blk.cross_attn_image_to_token
+            queries, A, c, B = tokens_back(queries, pts, ctx, att, blk.norm2, mlp=blk.mlp, norm3=blk.norm3,
+                                           next_attn=att2)
+            in_place = own and keys.shape[0] == N
+            keys = twoway_update(keys, pe, A, c, B, att2.out_proj.bias, blk.norm4.weight, blk.norm4.bias, blk.norm4.eps,
+                                 T, out=keys if in_place else None)
+            own = True
+        att = tr.final_attn_token_to_image
+        queries, qf = tokens_front(queries, pts, att)
+        ctx = twoway_pool(keys, pe, qf, T)
+        return tokens_back(queries, pts, ctx, att, tr.norm_final_attn), keys
